@@ -2,6 +2,12 @@
 """Benchmark: Ed25519 verifications/s at batch 2^20 per GPU (BASELINE.json metric).
 
 python bench.py [--gpus N] [--steps K] [--warmup W] [--n ITEMS_PER_GPU] [--global-n ITEMS]
+                [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it
+synthesises the batch, warms up, times the K steps, writes the last step's
+outputs if --dump-outputs is given, and prints the result line.  Everything
+listed under "Reported beside it" below runs with --full only.
 
 One process per GPU.  Launched under torch.distributed.run (RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* in the environment), every rank runs its shard.  Run
@@ -21,7 +27,15 @@ final bitmask gather.  --global-n 16777216 runs C5 (2^24 split over the ranks,
 strong scaling).  --dry-run exercises the launcher, sharding, timing and
 gather on CPU (gloo, no GPU, no verification) for tests/test_bench_launcher.py.
 
-Reported beside it:
+--dump-outputs DIR writes what the last timed step computed, as the caller of
+verify_device receives it: DIR/flags.npy (the per-item flag bytes, float32) and
+DIR/strict_bits.npy (the packed STRICT_OK words, as unsigned values in
+float64); rank r > 0 of a multi-GPU run writes flags_rank<r>.npy and
+strict_bits_rank<r>.npy.  The inputs are seeded, so two runs with the same
+arguments verify identical batches.  An output of more than 2^22 elements is
+written as a fixed, seeded sample of 2^22 of them (in index order).
+
+Reported beside it (--full):
   roofline         int32-VALU bound; achieved = 192,000 u32 MACs per verification
                    (SURVEY 8(d) convention) x items per launch / GPU time per step
                    from HIP events around the timed steps; isolated_launch_ms is
@@ -55,9 +69,10 @@ Each rank binds its threads to its GPU's NUMA node before any measurement
 the other socket of a two-socket host measured up to 9 us slower
 (profiles/r05ac_numa.txt).
 
-stdout carries ONE compact JSON line (< 4 KB: the C4 line, roofline,
-cpu_baseline, and a `latency` object with every GPU latency next to the CPU
-port's); the full record (every rep's phases and tails) goes to --detail.
+stdout carries ONE compact JSON line: the C4 line and the roofline figures of
+the timed steps; with --full (< 4 KB) also the checks, cpu_baseline, and a
+`latency` object with every GPU latency next to the CPU port's, and the full
+record (every rep's phases and tails) goes to --detail.
 """
 import argparse
 import ctypes
@@ -775,14 +790,17 @@ def compact(out):
     c["roofline"] = {"bound": rf["bound"], "achieved": _r(rf["achieved"]), "peak": _r(rf["peak"]), "unit": rf["unit"],
                      "frac": _r(rf["frac"]), "traffic": _r(rf["traffic"]),
                      "traffic_unit": "HBM B/launch (PMC FETCH_SIZEx2+WRITE_SIZE, committed pass)",
-                     "kernel_ms": _r(rf["kernel_ms"]), "isolated_launch_ms": _r(rf["isolated_launch_ms"]),
-                     "frac_isolated_launch": _r(rf["frac_isolated_launch"]),
+                     "kernel_ms": _r(rf["kernel_ms"]),
                      "work": "192000 u32 MAC/verif; 129 B/verif algorithmic"}
+    if "isolated_launch_ms" in rf:  # --full
+        c["roofline"]["isolated_launch_ms"] = _r(rf["isolated_launch_ms"])
+        c["roofline"]["frac_isolated_launch"] = _r(rf["frac_isolated_launch"])
     if len(rf.get("per_rank", [])) > 1:
         c["roofline"]["per_rank_kernel_ms"] = [_r(r["kernel_ms"]) for r in rf["per_rank"]]
-    ck = out["checks"]
-    c["checks"] = {k: ck[k] for k in ("honest_all_accepted", "corrupted_all_rejected", "outputs_identical_across_streams",
-                                      "device_self_check_faults")}
+    ck = out.get("checks")
+    if ck:  # --full
+        c["checks"] = {k: ck[k] for k in ("honest_all_accepted", "corrupted_all_rejected",
+                                          "outputs_identical_across_streams", "device_self_check_faults")}
     cb = out.get("cpu_baseline")
     if cb:
         c["cpu_baseline"] = {"value": _r(cb["value"]), "unit": cb["unit"], "cores": cb["cores"], "kind": cb["kind"],
@@ -854,8 +872,28 @@ def compact(out):
                            "cpu_tx_per_s": _r(mp.get("cpu_baseline", {}).get("value"))}
     if "qc_cpu_baseline" in out:
         c["qc_cpu_cores"] = out["qc_cpu_baseline"]["cores"]
-    c["detail"] = out.get("detail_path")
+    if "detail_path" in out:
+        c["detail"] = out["detail_path"]
     return c
+
+
+DUMP_MAX = 1 << 22  # elements per dumped array (flags: 16 MB as float32)
+
+
+def dump_outputs(dirpath, rank, flags, bits):
+    """--dump-outputs: what verify_device left in the caller's two output
+    tensors in the last timed step, one .npy each.  The flag bytes fit float32;
+    the packed STRICT_OK words are written as their unsigned values, which
+    float64 holds exactly.  An array of more than DUMP_MAX elements is written
+    as a seeded sample of DUMP_MAX of them, in index order."""
+    os.makedirs(dirpath, exist_ok=True)
+    tag = f"_rank{rank}" if rank else ""
+    arrays = {"flags": flags.cpu().numpy().astype(np.float32),
+              "strict_bits": bits.cpu().numpy().view(np.uint32).astype(np.float64)}
+    for name, arr in arrays.items():
+        if arr.size > DUMP_MAX:
+            arr = arr[np.sort(np.random.default_rng(0xD0).choice(arr.size, DUMP_MAX, replace=False))]
+        np.save(os.path.join(dirpath, f"{name}{tag}.npy"), arr)
 
 
 def parse_args(argv=None):
@@ -882,8 +920,15 @@ def parse_args(argv=None):
     ap.add_argument("--global-n", type=int, default=None,
                     help="C5 strong scaling: total triples split over the ranks (e.g. 16777216 = 2^24); "
                          "default: weak scaling with --n per GPU")
-    ap.add_argument("--detail", default=os.path.join("gpurun_out", "bench_detail.json"),
-                    help="file for the full record (every rep's phases, tails, probes); stdout gets the compact line")
+    ap.add_argument("--detail", default="bench_detail.json",
+                    help="with --full: file for the full record (every rep's phases, tails, probes); stdout gets "
+                         "the compact line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything reported beside the headline figure: output "
+                         "checks, one-launch time and peak probe, mempool and host-buffer lines, CPU baselines, "
+                         "latency legs, committee cache (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--tc-seq-reps", type=int, default=30,
                     help="repetitions of the 667-call sequential TC loop (tc_dropin_sequential)")
     ap.add_argument("--launched-child", action="store_true", help=argparse.SUPPRESS)
@@ -968,6 +1013,8 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world > 1 and not a.qc:
         a.no_qc = True
+    if not a.full:  # a plain run: the timed steps, the outputs if asked for, the result line
+        a.no_qc = a.no_cpu_baseline = True
 
     import torch.distributed as dist
     if a.dry_run:
@@ -1040,17 +1087,21 @@ def main():
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t_start
     kernel_ms = e0.elapsed_time(e1) / a.steps
-    # one launch alone on one stream (outside the timed region): the per-launch
-    # duration rocprofv3 reports for the two kernels
-    i0, i1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    i0.record(stream)
-    for _ in range(3):
-        verifier.verify_device(pk, sig, msg, flags, bits, stream=stream.cuda_stream)
-    i1.record(stream)
-    torch.cuda.synchronize(dev)
-    isolated_ms = i0.elapsed_time(i1) / 3
-    same_out = all(torch.equal(outs[0][0], o[0]) and torch.equal(outs[0][1], o[1]) for o in outs[1:])
-    mine = {"rank": rank, "kernel_ms": kernel_ms, "isolated_launch_ms": isolated_ms, "elapsed_s": elapsed}
+    if a.dump_outputs and a.steps > 0:
+        dump_outputs(a.dump_outputs, rank, *outs[(a.steps - 1) % nst])
+    mine = {"rank": rank, "kernel_ms": kernel_ms, "elapsed_s": elapsed}
+    if a.full:
+        # one launch alone on one stream (outside the timed region): the per-launch
+        # duration rocprofv3 reports for the two kernels
+        i0, i1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        i0.record(stream)
+        for _ in range(3):
+            verifier.verify_device(pk, sig, msg, flags, bits, stream=stream.cuda_stream)
+        i1.record(stream)
+        torch.cuda.synchronize(dev)
+        isolated_ms = i0.elapsed_time(i1) / 3
+        same_out = all(torch.equal(outs[0][0], o[0]) and torch.equal(outs[0][1], o[1]) for o in outs[1:])
+        mine["isolated_launch_ms"] = isolated_ms
     per_rank = [mine]
     if world > 1:
         dist.barrier()
@@ -1062,19 +1113,20 @@ def main():
     for r in per_rank:
         r["frac"] = a.n * WORK_MACS / (r["kernel_ms"] * 1e-3) / PEAK_MACS
 
-    f = flags.cpu().numpy()
-    honest_ok = bool((f[w.accept] & 1).all())
-    corrupt_rejected = bool(not (f[~w.accept] & 1).any())
-    faults = verifier.device_faults(local_rank)  # device self-checks of every launch above
-    global_accepted = int((f & 1).sum())
-    if world > 1:
-        # host gather of the per-signature STRICT_OK bitmask (outside the timed region)
-        from hsverify import dist as hd
-        strict_all = hd.gather_strict(f, a.n * world)
-        honest_all = hd.gather_strict(w.accept.astype(np.uint8), a.n * world)
-        honest_ok = bool(strict_all[honest_all].all())
-        corrupt_rejected = bool(not strict_all[~honest_all].any())
-        global_accepted = int(strict_all.sum())
+    if a.full:
+        f = flags.cpu().numpy()
+        honest_ok = bool((f[w.accept] & 1).all())
+        corrupt_rejected = bool(not (f[~w.accept] & 1).any())
+        faults = verifier.device_faults(local_rank)  # device self-checks of every launch above
+        global_accepted = int((f & 1).sum())
+        if world > 1:
+            # host gather of the per-signature STRICT_OK bitmask (outside the timed region)
+            from hsverify import dist as hd
+            strict_all = hd.gather_strict(f, a.n * world)
+            honest_all = hd.gather_strict(w.accept.astype(np.uint8), a.n * world)
+            honest_ok = bool(strict_all[honest_all].all())
+            corrupt_rejected = bool(not strict_all[~honest_all].any())
+            global_accepted = int(strict_all.sum())
 
     if rank != 0:
         if world > 1:
@@ -1084,7 +1136,6 @@ def main():
 
     total = a.n * world * a.steps
     value = total / elapsed
-    probe = verifier.measure_mad_peak()
     achieved = a.n * WORK_MACS / (kernel_ms * 1e-3)
     traffic, traffic_src = pmc_traffic(verifier.get_variant(), a.n)
     out = {
@@ -1121,21 +1172,23 @@ def main():
             "traffic_unit": "HBM bytes per launch (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE)",
             "traffic_source": traffic_src,
             "algorithmic_bytes_per_launch": a.n * IO_BYTES,
-            "peak_probe": probe / 1e12,
             "work_per_verify": f"{WORK_MACS} u32 MACs (SURVEY 8(d)); {IO_BYTES} HBM bytes algorithmic",
             "kernel_ms": kernel_ms,
             "kernel_ms_is": (f"GPU time per step, HIP events around the {a.steps} steps "
                              f"(consecutive launches on {nst} alternating streams)"),
-            "isolated_launch_ms": isolated_ms,
-            "frac_isolated_launch": a.n * WORK_MACS / (isolated_ms * 1e-3) / PEAK_MACS,
             "kernels": "hsv_prep_kernel + hsv_verify_hp_kernel (one verify launch: scalar prepass, point pass)",
             "per_rank": per_rank,
         },
-        "checks": {"honest_all_accepted": honest_ok, "corrupted_all_rejected": corrupt_rejected,
-                   "strict_accepted_global": global_accepted, "outputs_identical_across_streams": same_out,
-                   "device_self_check_faults": faults,
-                   "expected_accept": "honest items and the mixed-order-A items with k = 0 mod 8"},
     }
+    if a.full:
+        out["roofline"].update({
+            "peak_probe": verifier.measure_mad_peak() / 1e12,
+            "isolated_launch_ms": isolated_ms,
+            "frac_isolated_launch": a.n * WORK_MACS / (isolated_ms * 1e-3) / PEAK_MACS})
+        out["checks"] = {"honest_all_accepted": honest_ok, "corrupted_all_rejected": corrupt_rejected,
+                         "strict_accepted_global": global_accepted, "outputs_identical_across_streams": same_out,
+                         "device_self_check_faults": faults,
+                         "expected_accept": "honest items and the mixed-order-A items with k = 0 mod 8"}
     if not a.no_qc:
         # The two lines compared with the C4 line run right after it, in the same
         # conditions: the mempool line (the same point pass behind a message-hash
@@ -1173,7 +1226,7 @@ def main():
                 if chk is not None:
                     out["mempool_tx"]["cpu_baseline"] = mempool_cpu(chk)
                 out["qc_cpu_baseline"] = qc_cpu()
-    if a.detail:
+    if a.full and a.detail:
         try:
             os.makedirs(os.path.dirname(os.path.abspath(a.detail)), exist_ok=True)
             with open(a.detail, "w") as fh:

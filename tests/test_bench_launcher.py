@@ -51,3 +51,68 @@ def test_launcher_strong_scaling_global_n():
 def test_world_size_mismatch_is_an_error():
     r = _run(["--gpus", "2", "--dry-run"], env_extra={"WORLD_SIZE": "3", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0 and "WORLD_SIZE" in (r.stderr + r.stdout)
+
+
+def test_dump_outputs_formats_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 flag bytes, the packed words as exact unsigned
+    values in float64, and the same seeded sample of an oversized array each
+    time."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX", 1000)
+    rng = np.random.default_rng(1)
+    flags = rng.integers(0, 256, 4099, dtype=np.uint8)
+    bits = rng.integers(-2**31, 2**31, 129, dtype=np.int64).astype(np.int32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), 0, torch.from_numpy(flags), torch.from_numpy(bits))
+    f, b = np.load(tmp_path / "a" / "flags.npy"), np.load(tmp_path / "a" / "strict_bits.npy")
+    assert f.dtype == np.float32 and b.dtype == np.float64
+    assert np.array_equal(b, bits.view(np.uint32).astype(np.float64))      # 129 <= DUMP_MAX: whole
+    assert f.shape == (1000,) and set(np.unique(f)) <= set(np.unique(flags).astype(np.float32))
+    assert np.array_equal(f, np.load(tmp_path / "b" / "flags.npy"))
+    bench.dump_outputs(str(tmp_path / "a"), 1, torch.from_numpy(flags), torch.from_numpy(bits))
+    assert (tmp_path / "a" / "flags_rank1.npy").exists()
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_outputs(tmp_path):
+    """A plain run prints the headline line only (no --full legs) and
+    --dump-outputs holds what the last timed step computed: the expected
+    verify_strict result of every seeded item, in both output forms."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "hotstuff-digital-signature-benchmarking_amd"))
+    from hsverify import synth
+    n = 4099
+    r = _run(["--gpus", "1", "--n", str(n), "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    (j,) = _json_lines(r.stdout)
+    assert j["steps"] == 4 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["unit"] == "verif/s"
+    assert j["higher_is_better"] is True and j["dtype"] == "u32"
+    assert abs(j["value"] - n * 4 / (j["ms_per_step"] * 4e-3)) <= 1e-3 * j["value"]
+    for leg in ("checks", "latency", "cpu_baseline", "mempool_tx", "host_api", "detail"):
+        assert leg not in j
+    assert "isolated_launch_ms" not in j["roofline"]
+    assert sorted(os.listdir(tmp_path)) == ["flags.npy", "strict_bits.npy"]
+    flags, words = np.load(tmp_path / "flags.npy"), np.load(tmp_path / "strict_bits.npy")
+    assert flags.dtype == np.float32 and flags.shape == (n,)
+    assert words.dtype == np.float64 and words.shape == ((n + 31) // 32,)
+    accept = synth.independent_triples(n, seed=0xC4 * 1000, corrupt_frac=0.05).accept
+    strict = flags.astype(np.uint8) & 1
+    assert np.array_equal(strict.astype(bool), accept)
+    unpacked = np.unpackbits(words.astype(np.uint32).view(np.uint8), bitorder="little")[:n]
+    assert np.array_equal(unpacked, strict)
+
+
+@pytest.mark.gpu
+def test_full_run_reports_the_checks_beside_the_line(tmp_path):
+    detail = tmp_path / "detail.json"
+    r = _run(["--gpus", "1", "--n", "4099", "--steps", "2", "--warmup", "1", "--full", "--no-qc", "--no-cpu-baseline",
+              "--detail", str(detail)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    (j,) = _json_lines(r.stdout)
+    assert j["checks"] == {"honest_all_accepted": True, "corrupted_all_rejected": True,
+                           "outputs_identical_across_streams": True, "device_self_check_faults": 0}
+    assert j["roofline"]["isolated_launch_ms"] > 0 and j["detail"] == str(detail)
+    assert json.loads(detail.read_text())["roofline"]["peak_probe"] > 0

@@ -28,7 +28,7 @@ def main():
             if kv:
                 k, _, v = kv.partition("=")
                 env[k] = v
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-launched"],
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-launched"],
                                capture_output=True, text=True, timeout=600, env=env)
             if r.returncode != 0:
                 print(lib, "failed", r.stderr[-2000:])

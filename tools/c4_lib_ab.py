@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Same-box A/B of the C4 line (bench.py --no-qc --no-cpu-baseline) between
+"""Same-box A/B of the C4 line (bench.py --full --no-qc --no-cpu-baseline) between
 library builds in hsverify/ (HSV_LIB), alternating fresh processes; prints
 each run's verif/s, ms per step and one-launch time, then the medians.
 python tools/c4_lib_ab.py [--rounds 3] LIB[@VAR=VALUE] [LIB[@VAR=VALUE] ...]
@@ -27,7 +27,7 @@ def main():
             if kv:
                 k, _, v = kv.partition("=")
                 env[k] = v
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-qc", "--no-cpu-baseline"],
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-qc", "--no-cpu-baseline"],
                                capture_output=True, text=True, timeout=300, env=env)
             if r.returncode != 0:
                 print(lib, "rc", r.returncode, r.stderr[-1500:])

@@ -8,7 +8,7 @@ if [ -z "$NO_TESTS" ]; then
   step pytest; timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $OUT/${TAG}_pytest_gpu.txt 2>&1; rc=$?
   tail -2 $OUT/${TAG}_pytest_gpu.txt; [ $rc -eq 0 ] || exit $rc
 fi
-step bench; timeout -k 10 700 python bench.py $BENCH_ARGS > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; rc=$?
+step bench; timeout -k 10 700 python bench.py --full $BENCH_ARGS > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; rc=$?
 [ $rc -eq 0 ] || { tail -5 $OUT/${TAG}_bench.err; exit $rc; }
 python -c "
 import json; d=json.load(open('$OUT/${TAG}_bench.json')); r=d['roofline']

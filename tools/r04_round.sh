@@ -27,7 +27,7 @@ for st in $STAGES; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/${TAG}_smoke.txt 2>&1; rc=$?
       tail -1 $OUT/${TAG}_smoke.txt; fatal $rc $st ;;
     bench)
-      timeout -k 10 700 python bench.py $BENCH_ARGS > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; rc=$?
+      timeout -k 10 700 python bench.py --full $BENCH_ARGS > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; rc=$?
       [ $rc -eq 0 ] || tail -5 $OUT/${TAG}_bench.err
       python -c "
 import json; d=json.load(open('$OUT/${TAG}_bench.json')); r=d['roofline']
