@@ -186,6 +186,28 @@ hipError_t hsv_launch_tx_mask(const uint64_t *offsets, uint32_t n, uint8_t *flag
 }
 #endif
 
+// ---- batch signer (hsv_signer.hip) -----------------------------------------
+#ifdef __cplusplus
+extern "C" {
+#endif
+// One launch each, at most 2^22 items, enqueued on `stream` (no
+// synchronisation); comb16: the wide comb of B; fault: as hsv_launch_verify
+// (fault[0] only).  seeds (n * 32 B), keys (96-byte records a | prefix | pk)
+// and sig / sig_stride are 16-byte aligned; msg may have any alignment.
+hipError_t hsv_launch_keygen(const uint8_t *seeds, uint32_t n, uint8_t *keys, const uint32_t *comb16,
+                             uint32_t *fault, hipStream_t stream);
+// item i: key key_idx[i] (NULL: key i; an index >= nkeys writes a zero
+// signature), message msg + i * msg_stride of msg_len bytes
+hipError_t hsv_launch_sign(const uint8_t *keys, uint32_t nkeys, const uint32_t *key_idx, const uint8_t *msg,
+                           uint64_t msg_len, uint64_t msg_stride, uint32_t m, uint8_t *sig, uint64_t sig_stride,
+                           const uint32_t *comb16, uint32_t *fault, hipStream_t stream);
+// Items per lane (G) of the following signer launches: one of the built
+// values (1, 2, 4, 8, 16), 0 = the product's; previous value or -1.
+int hsvi_set_signer_group(int g);
+#ifdef __cplusplus
+}
+#endif
+
 // ---- error reporting shared by the C-ABI translation units -----------------
 #ifdef __cplusplus
 extern "C" {

@@ -1,0 +1,143 @@
+// gfx950 kernels of the batch signer (hsv_signer_*, include/hsv.h).
+//
+//  hsv_keygen_kernel  seeds -> 96-byte expanded key records a | prefix | pk
+//  hsv_sign_kernel    (key record, message) -> R || s
+//
+// Both run csrc/hsv_sign_core.hpp's lane functions on a plain grid: a wave
+// takes 64 * G consecutive items, lane l the items base + g * 64 + l (g < G),
+// so every load and store of a wave is coalesced.  The state an item keeps
+// between the two phases (its point, the prefix product before it, r: 49
+// words) sits in a launch workspace from the library pool, word by word across
+// the wave's lanes; nothing is handed between waves, so there is no work
+// counter and no persistent loop.  [r]B reads the wide comb of B the device
+// context already holds (16 reads of 96 bytes per item, MALL-resident).
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+
+#include "hsv_internal.h"
+#include "hsv_sign_core.hpp"
+
+namespace hsv {
+
+constexpr int kSignBlock = 256;
+
+// Slot g, word w of this lane: base[(g * kSignWsWords + w) * 64] -- one word of
+// all 64 lanes is one 256-byte line.
+struct LaneStore {
+  uint32_t *base;
+  __device__ __forceinline__ void put(int g, int w, uint32_t v) { base[(uint32_t)(g * kSignWsWords + w) * 64u] = v; }
+  __device__ __forceinline__ uint32_t get(int g, int w) const { return base[(uint32_t)(g * kSignWsWords + w) * 64u]; }
+};
+
+template <int G>
+__global__ void __launch_bounds__(kSignBlock) hsv_keygen_kernel(KeygenArgs a, uint32_t *__restrict__ ws,
+                                                                uint32_t *__restrict__ fault) {
+  const uint32_t wave = blockIdx.x * (kSignBlock / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  const uint64_t base = (uint64_t)wave * 64u * G;
+  if (base >= a.n) return;  // the whole wave is past the end
+  LaneStore st{ws + (uint64_t)wave * G * kSignWsWords * 64u + lane};
+  a.inject = kInjectNone;
+  if (keygen_lane<16, G>(a, base + lane, 64u, st)) fault[0] = 1u;  // device self-check (hsv_pointpass.hpp report_faults)
+}
+
+template <int G, bool FAST>
+__global__ void __launch_bounds__(kSignBlock) hsv_sign_kernel(SignArgs a, uint32_t *__restrict__ ws,
+                                                              uint32_t *__restrict__ fault) {
+  const uint32_t wave = blockIdx.x * (kSignBlock / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  const uint64_t base = (uint64_t)wave * 64u * G;
+  if (base >= a.m) return;  // the whole wave is past the end
+  LaneStore st{ws + (uint64_t)wave * G * kSignWsWords * 64u + lane};
+  a.inject = kInjectNone;
+  if (sign_lane<16, G, FAST>(a, base + lane, 64u, st)) fault[0] = 1u;
+}
+
+}  // namespace hsv
+
+namespace {
+
+constexpr int kGroups[] = {1, 2, 4, 8, 16};
+std::atomic<int> g_group{hsv::kSignGroup};
+
+struct Grid {
+  uint32_t blocks;
+  size_t ws_bytes;
+};
+Grid grid_for(uint64_t n, int group) {
+  const uint64_t per_block = (uint64_t)hsv::kSignBlock * group;
+  const uint64_t blocks = (n + per_block - 1) / per_block;
+  return {(uint32_t)blocks, (size_t)(blocks * per_block * hsv::kSignWsWords * sizeof(uint32_t))};
+}
+
+template <int G>
+void launch_keygen(const hsv::KeygenArgs &a, uint32_t blocks, uint32_t *ws, uint32_t *fault, hipStream_t stream) {
+  hipLaunchKernelGGL((hsv::hsv_keygen_kernel<G>), dim3(blocks), dim3(hsv::kSignBlock), 0, stream, a, ws, fault);
+}
+
+template <int G>
+void launch_sign(const hsv::SignArgs &a, uint32_t blocks, uint32_t *ws, uint32_t *fault, hipStream_t stream) {
+  if (a.msg_len == 32)
+    hipLaunchKernelGGL((hsv::hsv_sign_kernel<G, true>), dim3(blocks), dim3(hsv::kSignBlock), 0, stream, a, ws, fault);
+  else
+    hipLaunchKernelGGL((hsv::hsv_sign_kernel<G, false>), dim3(blocks), dim3(hsv::kSignBlock), 0, stream, a, ws, fault);
+}
+
+}  // namespace
+
+// G of the following launches (measurement hook, csrc/hsv_test_hooks.h):
+// 0 restores the product's; returns the previous value, or -1 for a value
+// that is not built.
+extern "C" int hsvi_set_signer_group(int g) {
+  if (g == 0) g = hsv::kSignGroup;
+  for (int b : kGroups)
+    if (b == g) return g_group.exchange(g);
+  return -1;
+}
+
+extern "C" hipError_t hsv_launch_keygen(const uint8_t *seeds, uint32_t n, uint8_t *keys, const uint32_t *comb16,
+                                        uint32_t *fault, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  if (n > (1u << 22)) return hipErrorInvalidValue;
+  const int group = g_group.load();
+  const Grid gr = grid_for(n, group);
+  void *ws = nullptr;
+  hipError_t e = hsv_ws_malloc(&ws, gr.ws_bytes, stream);
+  if (e != hipSuccess) return e;
+  const hsv::KeygenArgs a{seeds, n, keys, comb16, hsv::kInjectNone, 0u};
+  uint32_t *w = static_cast<uint32_t *>(ws);
+  switch (group) {
+    case 1: launch_keygen<1>(a, gr.blocks, w, fault, stream); break;
+    case 2: launch_keygen<2>(a, gr.blocks, w, fault, stream); break;
+    case 4: launch_keygen<4>(a, gr.blocks, w, fault, stream); break;
+    case 8: launch_keygen<8>(a, gr.blocks, w, fault, stream); break;
+    default: launch_keygen<16>(a, gr.blocks, w, fault, stream); break;
+  }
+  e = hipGetLastError();
+  const hipError_t ef = hipFreeAsync(ws, stream);
+  return e != hipSuccess ? e : ef;
+}
+
+extern "C" hipError_t hsv_launch_sign(const uint8_t *keys, uint32_t nkeys, const uint32_t *key_idx, const uint8_t *msg,
+                                      uint64_t msg_len, uint64_t msg_stride, uint32_t m, uint8_t *sig,
+                                      uint64_t sig_stride, const uint32_t *comb16, uint32_t *fault,
+                                      hipStream_t stream) {
+  if (m == 0) return hipSuccess;
+  if (m > (1u << 22)) return hipErrorInvalidValue;
+  const int group = g_group.load();
+  const Grid gr = grid_for(m, group);
+  void *ws = nullptr;
+  hipError_t e = hsv_ws_malloc(&ws, gr.ws_bytes, stream);
+  if (e != hipSuccess) return e;
+  const hsv::SignArgs a{keys, nkeys, key_idx, msg, msg_len, msg_stride, m, sig, sig_stride, comb16, hsv::kInjectNone, 0u};
+  uint32_t *w = static_cast<uint32_t *>(ws);
+  switch (group) {
+    case 1: launch_sign<1>(a, gr.blocks, w, fault, stream); break;
+    case 2: launch_sign<2>(a, gr.blocks, w, fault, stream); break;
+    case 4: launch_sign<4>(a, gr.blocks, w, fault, stream); break;
+    case 8: launch_sign<8>(a, gr.blocks, w, fault, stream); break;
+    default: launch_sign<16>(a, gr.blocks, w, fault, stream); break;
+  }
+  e = hipGetLastError();
+  const hipError_t ef = hipFreeAsync(ws, stream);
+  return e != hipSuccess ? e : ef;
+}

@@ -1,0 +1,193 @@
+// C ABI of the batch signer (include/hsv.h, hsv_signer_*): the GPU form of
+//   crypto::generate_keypair  (reference crypto/src/lib.rs:167-175)
+//   crypto::Signature::new    (reference crypto/src/lib.rs:185-191)
+// A signer holds, in HBM of the device bound at creation, one 96-byte
+// expanded record a | prefix | pk per key (hsv_keygen_kernel) and signs from
+// them with hsv_sign_kernel (csrc/hsv_signer.hip).  There is no CPU fallback:
+// hsv_sign_many is the host signer.
+#include <algorithm>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "hsv_host.h"
+
+using namespace hsvh;
+
+struct hsv_signer {
+  int device = 0;
+  size_t n = 0;
+  uint8_t *d_keys = nullptr;   // n records of 96 B
+  std::vector<uint8_t> h_pks;  // n * 32 B
+};
+
+namespace {
+
+// launches of at most kChunk items, one after the other on `stream`
+hipError_t sign_chunks(const hsv_signer &s, const uint32_t *d_key_idx, const uint8_t *d_msg, size_t msg_len,
+                       size_t msg_stride, size_t m, uint8_t *d_sig, size_t sig_stride, const uint32_t *comb16,
+                       uint32_t *fault, hipStream_t stream) {
+  hipError_t e = hipSuccess;
+  for (size_t base = 0; base < m && e == hipSuccess; base += kChunk) {
+    const size_t k = std::min(kChunk, m - base);
+    // key_idx == NULL: item i uses key i, so a chunk's records start at its base
+    e = hsv_launch_sign(s.d_keys + (d_key_idx ? 0 : base * 96), (uint32_t)(d_key_idx ? s.n : s.n - base),
+                        d_key_idx ? d_key_idx + base : nullptr, d_msg + base * msg_stride, msg_len, msg_stride,
+                        (uint32_t)k, d_sig + base * sig_stride, sig_stride, comb16, fault, stream);
+  }
+  return e;
+}
+
+int sign_args_ok(const hsv_signer *s, const uint32_t *key_idx, const void *msg, size_t msg_len, size_t msg_stride,
+                 size_t m, const void *sig) {
+  if (!s || !sig || (!msg && msg_len)) return fail(HSV_ERR_INVALID_ARG, "null argument");
+  if (msg_stride != 0 && msg_stride < msg_len) return fail(HSV_ERR_INVALID_ARG, "messages overlap");
+  if (m > 0xffffffffu) return fail(HSV_ERR_INVALID_ARG, "batch too large");
+  if (!key_idx && m > s->n) return fail(HSV_ERR_INVALID_ARG, "more items than keys and no key_idx");
+  return HSV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hsv_signer_create(const uint8_t *seeds, size_t nkeys, hsv_signer **out) {
+  if (!out || (!seeds && nkeys)) return fail(HSV_ERR_INVALID_ARG, "null argument");
+  if (nkeys > 0xffffffffu) return fail(HSV_ERR_INVALID_ARG, "too many keys");
+  int rc = ensure_init();
+  if (rc != HSV_OK) return rc;
+  const int dev = home_device();
+  DeviceGuard guard(dev);
+  if (guard.status() != hipSuccess) return hip_fail("hipSetDevice", guard.status());
+  DevCtx &c = ctx(dev);
+  rc = ensure_btable16(c);
+  if (rc != HSV_OK) return rc;
+  std::unique_ptr<hsv_signer> s(new hsv_signer());
+  s->device = dev;
+  s->n = nkeys;
+  s->h_pks.resize(nkeys * 32);
+  if (nkeys) {
+    uint8_t *d_seeds = nullptr;
+    uint32_t *d_fault = nullptr;
+    hipStream_t st = nullptr;
+    uint8_t words[kFaultBytes] = {0};
+    hipError_t e = hipMalloc(&s->d_keys, nkeys * 96);
+    if (e == hipSuccess) e = hipMalloc(&d_seeds, nkeys * 32);
+    if (e == hipSuccess) e = hipMalloc(&d_fault, 256);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_seeds, seeds, nkeys * 32, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_fault, 0, kFaultBytes, st);
+    for (size_t base = 0; base < nkeys && e == hipSuccess; base += kChunk)
+      e = hsv_launch_keygen(d_seeds + base * 32, (uint32_t)std::min(kChunk, nkeys - base), s->d_keys + base * 96,
+                            c.d_btable16, d_fault, st);
+    if (e == hipSuccess)
+      e = hipMemcpy2DAsync(s->h_pks.data(), 32, s->d_keys + 64, 96, 32, nkeys, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(words, d_fault, kFaultBytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (st) (void)hipStreamDestroy(st);
+    {
+      ResidentPause pause;  // hipFree waits for every grid on the device
+      if (d_seeds) (void)hipFree(d_seeds);
+      if (d_fault) (void)hipFree(d_fault);
+    }
+    if (e == hipSuccess) rc = check_faults(words, "hsv_signer_create");
+    if (e != hipSuccess || rc != HSV_OK) {
+      hsv_signer_destroy(s.release());
+      return e != hipSuccess ? hip_fail("expanding the signer's keys", e) : rc;
+    }
+  }
+  *out = s.release();
+  return HSV_OK;
+}
+
+void hsv_signer_destroy(hsv_signer *s) {
+  if (!s) return;
+  if (s->d_keys) {
+    ResidentPause pause;  // hipFree waits for every grid on the device
+    DeviceGuard guard(s->device);
+    (void)hipFree(s->d_keys);
+  }
+  delete s;
+}
+
+size_t hsv_signer_size(const hsv_signer *s) { return s ? s->n : 0; }
+
+int hsv_signer_public_keys(const hsv_signer *s, uint8_t *pk_out) {
+  if (!s || (!pk_out && s->n)) return fail(HSV_ERR_INVALID_ARG, "null argument");
+  if (s->n) std::memcpy(pk_out, s->h_pks.data(), s->n * 32);
+  return HSV_OK;
+}
+
+int hsv_signer_sign_device(const hsv_signer *s, const uint32_t *d_key_idx, const uint8_t *d_msg, size_t msg_len,
+                           size_t msg_stride, size_t m, uint8_t *d_sig, size_t sig_stride, uint32_t *d_fault,
+                           void *stream) {
+  if (m == 0) return HSV_OK;
+  // misaligned pointers are rejected before anything is looked at (as hsv_verify_device)
+  if (((reinterpret_cast<uintptr_t>(d_sig) | sig_stride) & 15u) != 0)
+    return fail(HSV_ERR_ALIGN, "d_sig and sig_stride must be multiples of 16");
+  if (reinterpret_cast<uintptr_t>(d_key_idx) & 3u) return fail(HSV_ERR_ALIGN, "d_key_idx must be 4-byte aligned");
+  int rc = sign_args_ok(s, d_key_idx, d_msg, msg_len, msg_stride, m, d_sig);
+  if (rc != HSV_OK) return rc;
+  if (sig_stride < 64) return fail(HSV_ERR_INVALID_ARG, "signatures overlap");
+  rc = ensure_init();
+  if (rc != HSV_OK) return rc;
+  const int pd = pointer_device(d_sig);
+  if (pd >= 0 && pd != s->device)
+    return fail(HSV_ERR_INVALID_ARG, "buffers live on device " + std::to_string(pd) + ", the signer on device " +
+                                         std::to_string(s->device));
+  DevCtx &c = ctx(s->device);
+  DeviceGuard guard(c.device);
+  if (guard.status() != hipSuccess) return hip_fail("hipSetDevice", guard.status());
+  rc = ensure_btable16(c);  // the B table is rebuilt if hsv_shutdown released it
+  if (rc != HSV_OK) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  uint32_t *fault = nullptr;
+  rc = call_fault_words(c, d_fault, st, &fault);
+  if (rc != HSV_OK) return rc;
+  const hipError_t e = sign_chunks(*s, d_key_idx, d_msg, msg_len, msg_stride, m, d_sig, sig_stride, c.d_btable16, fault, st);
+  return e == hipSuccess ? HSV_OK : hip_fail("sign kernel launch", e);
+}
+
+int hsv_signer_sign(hsv_signer *s, const uint32_t *key_idx, const uint8_t *msgs, size_t msg_len, size_t msg_stride,
+                    size_t m, uint8_t *sig_out) {
+  if (m == 0) return HSV_OK;
+  int rc = sign_args_ok(s, key_idx, msgs, msg_len, msg_stride, m, sig_out);
+  if (rc != HSV_OK) return rc;
+  rc = ensure_init();
+  if (rc != HSV_OK) return rc;
+  DevCtx &c = ctx(s->device);
+  DeviceGuard guard(c.device);
+  if (guard.status() != hipSuccess) return hip_fail("hipSetDevice", guard.status());
+  rc = ensure_btable16(c);
+  if (rc != HSV_OK) return rc;
+  SlotLease lease(c);
+  Slot &slot = lease.slot();
+  rc = slot_prepare(slot, 0, 0);
+  if (rc != HSV_OK) return rc;
+  hipStream_t st = slot.stream;
+  // one stream-ordered block from the library pool: signatures | fault words | key indices | messages
+  const size_t msg_bytes = msg_stride ? (m - 1) * msg_stride + msg_len : msg_len;
+  const size_t off_fault = m * 64, off_idx = off_fault + 256, off_msg = off_idx + round_up(key_idx ? m * 4 : 0, 256);
+  void *blk = nullptr;
+  hipError_t e = hsv_ws_malloc(&blk, off_msg + msg_bytes + 256, st);
+  if (e != hipSuccess) return hip_fail("allocating the signing buffers", e);
+  uint8_t *d = static_cast<uint8_t *>(blk);
+  uint32_t *d_fault = reinterpret_cast<uint32_t *>(d + off_fault);
+  uint32_t *d_idx = key_idx ? reinterpret_cast<uint32_t *>(d + off_idx) : nullptr;
+  uint8_t words[kFaultBytes] = {0};
+  e = hipMemsetAsync(d_fault, 0, kFaultBytes, st);
+  if (e == hipSuccess && key_idx) e = hipMemcpyAsync(d_idx, key_idx, m * 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && msg_bytes) e = hipMemcpyAsync(d + off_msg, msgs, msg_bytes, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess)
+    e = sign_chunks(*s, d_idx, d + off_msg, msg_len, msg_stride, m, d, 64, c.d_btable16, d_fault, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(sig_out, d, m * 64, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(words, d_fault, kFaultBytes, hipMemcpyDeviceToHost, st);
+  const hipError_t ef = hipFreeAsync(blk, st);
+  const hipError_t es = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = ef;
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return hip_fail("hsv_signer_sign", e);
+  return check_faults(words, "hsv_signer_sign");
+}
+
+}  // extern "C"

@@ -75,5 +75,6 @@ int hsv_test_tx_records(const uint8_t *d_txs, const uint64_t *d_offsets, size_t 
                                              reinterpret_cast<hipStream_t>(stream));
   return e == hipSuccess ? HSV_OK : HSV_ERR_HIP;
 }
+int hsv_test_signer_group(int g) { return hsvi_set_signer_group(g); }
 
 }  // extern "C"

@@ -74,6 +74,12 @@ HSV_API int hsv_test_resident_post_bad(uint32_t m);
  * form, without the verification). */
 HSV_API int hsv_test_tx_records(const uint8_t *d_txs, const uint64_t *d_offsets, size_t tx_size, size_t n,
                                 uint8_t *d_records, void *stream);
+/* Measurement (tools/sign_bench.py) and tests: items per lane (G) of the
+ * signer's following launches -- the batch over which one field inversion is
+ * shared (csrc/hsv_sign_core.hpp).  Built: 1 (unbatched), 2, 4, 8, 16; 0
+ * restores the product's.  Returns the previous value, or -1 for a value that
+ * is not built. */
+HSV_API int hsv_test_signer_group(int g);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,107 @@
+"""Batch Ed25519 key derivation and signing on the GPU (hsv_signer_*, include/hsv.h).
+
+The GPU form of the reference's ``generate_keypair`` and ``Signature::new``
+(crypto/src/lib.rs:167-175, 185-191) for load generators and input synthesis:
+``Signer(seeds)`` expands the seeds once into key records in HBM, and
+``sign`` / ``sign_device`` produce RFC 8032 signatures bit-exact with
+``verifier.sign_many``.  Not constant time (table lookups are indexed by
+secret digits): never use it to hold a validator's key.  There is no CPU
+fallback; without a GPU the constructor raises.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from . import _lib
+
+
+def _ptr(a: np.ndarray):
+    return ctypes.c_void_p(a.ctypes.data) if a.size else None
+
+
+class Signer:
+    def __init__(self, seeds):
+        if isinstance(seeds, (bytes, bytearray)):
+            seeds = np.frombuffer(bytes(seeds), np.uint8)
+        arr = np.ascontiguousarray(seeds, np.uint8).reshape(-1, 32)
+        self._lib = _lib.load()
+        self._h = ctypes.c_void_p()
+        _lib.check(self._lib.hsv_signer_create(_ptr(arr), arr.shape[0], ctypes.byref(self._h)), "hsv_signer_create")
+        self._n = arr.shape[0]
+
+    def __len__(self) -> int:
+        return self._n
+
+    def public_keys(self) -> np.ndarray:
+        """(nkeys, 32) uint8, in seed order."""
+        out = np.zeros((self._n, 32), np.uint8)
+        _lib.check(self._lib.hsv_signer_public_keys(self._h, _ptr(out)), "hsv_signer_public_keys")
+        return out
+
+    def sign(self, msgs, key_idx=None) -> np.ndarray:
+        """msgs: (m, L) uint8, one message per item, or (L,) one shared message
+        (then m = len(key_idx), or every key when key_idx is None).  key_idx:
+        (m,) key per item; None: item i uses key i.  An index >= nkeys gives 64
+        zero bytes.  Returns (m, 64) uint8, R || s."""
+        msgs = np.ascontiguousarray(msgs, np.uint8)
+        idx = None if key_idx is None else np.ascontiguousarray(key_idx, np.uint32).reshape(-1)
+        if msgs.ndim == 1:
+            m, length, stride = (self._n if idx is None else idx.size), msgs.size, 0
+        else:
+            m, length = msgs.shape
+            stride = length
+            if idx is not None and idx.size != m:
+                raise ValueError("key_idx and msgs differ in length")
+        out = np.zeros((m, 64), np.uint8)
+        if m:
+            _lib.check(self._lib.hsv_signer_sign(self._h, None if idx is None else _ptr(idx), _ptr(msgs), length,
+                                                 stride, m, _ptr(out)), "hsv_signer_sign")
+        return out
+
+    def sign_device(self, msg, sig, key_idx=None, msg_len=None, stream=None, fault=None) -> None:
+        """Device tensors, enqueued on ``stream`` (default: torch's current
+        stream), no synchronisation.  msg: (m, L) uint8 rows (any row stride) or
+        (L,) one shared message; sig: (m, >= 64) uint8 rows whose address and
+        stride are multiples of 16 -- a (m, 64) slice of packed pk||R||s
+        records works; key_idx: (m,) int32 / uint32 or None; msg_len: bytes of
+        each row that are signed (default: the row length L); fault: optional
+        per-call fault words (verifier.verify_device)."""
+        from .verifier import _fault_ptr
+        import torch
+        m = sig.shape[0]
+        for t in (msg, key_idx, fault):
+            if t is not None and t.device != sig.device:
+                raise ValueError(f"all tensors must live on {sig.device}, got {t.device}")
+        if msg.dim() == 1:
+            length, stride = msg.shape[0], 0
+        else:
+            length, stride = msg.shape[1], msg.stride(0)
+        if msg_len is not None:
+            length = msg_len
+        with torch.cuda.device(sig.device):
+            if stream is None:
+                stream = torch.cuda.current_stream(sig.device).cuda_stream
+            rc = self._lib.hsv_signer_sign_device(
+                self._h, ctypes.c_void_p(key_idx.data_ptr()) if key_idx is not None else None,
+                ctypes.c_void_p(msg.data_ptr()), length, stride, m, ctypes.c_void_p(sig.data_ptr()), sig.stride(0),
+                _fault_ptr(fault), ctypes.c_void_p(stream))
+        _lib.check(rc, "hsv_signer_sign_device")
+
+    def close(self) -> None:
+        if self._h:
+            self._lib.hsv_signer_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

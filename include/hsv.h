@@ -8,8 +8,8 @@
  *   crypto::Signature::verify_batch  crypto/src/lib.rs:210-223  -> hsv_verify_batch
  *                                                                   hsv_verify_batch_packed
  *   (batched strict API)                     -> hsv_verify
- *   crypto::Signature::new           crypto/src/lib.rs:185-191  -> hsv_sign
- *   crypto::generate_keypair         crypto/src/lib.rs:167-175  -> hsv_public_key
+ *   crypto::Signature::new           crypto/src/lib.rs:185-191  -> hsv_sign, hsv_signer_sign*
+ *   crypto::generate_keypair         crypto/src/lib.rs:167-175  -> hsv_public_key, hsv_signer_create
  *   mempool transaction check  mempool/src/batch_maker.rs:79-85 -> hsv_verify_transactions*
  *   QC / TC signature checks from wire bytes
  *                        consensus/src/messages.rs:180-198, 290-315 -> hsv_qc_verify_bincode,
@@ -295,6 +295,45 @@ HSV_API int hsv_sign(const uint8_t seed[32], const uint8_t *msg, size_t msg_len,
  * keys and n signatures.  nthreads <= 0 picks min(hardware concurrency, 16). */
 HSV_API int hsv_sign_many(const uint8_t *seeds, const uint8_t *msgs, size_t msg_len, size_t n,
                   uint8_t *pk_out, uint8_t *sig_out, int nthreads);
+
+/* ---- signing and key derivation on the GPU (batch) ----------------------- */
+/* The GPU form of generate_keypair and Signature::new for load generators and
+ * input synthesis: a signer expands its seeds once into 96-byte records
+ * a | prefix | pk in HBM of the device bound at creation (hsv_init, as a
+ * committee) and then signs batches from them, bit-exact with hsv_sign /
+ * hsv_sign_many (RFC 8032, deterministic).
+ * NOT constant time: [r]B and [a]B are sums of entries of the B comb table,
+ * and those lookups are indexed by digits of the secret scalars.  This path is
+ * for load generation and synthesising inputs, never for custody of a
+ * validator key.  There is no CPU fallback: without a GPU every call below
+ * returns HSV_ERR_NO_DEVICE (hsv_sign_many is the host signer). */
+typedef struct hsv_signer hsv_signer;
+/* Expand nkeys seeds (nkeys*32 B) on the GPU.  nkeys == 0 gives an empty signer. */
+HSV_API int hsv_signer_create(const uint8_t *seeds, size_t nkeys, hsv_signer **out);
+HSV_API void hsv_signer_destroy(hsv_signer *s);
+HSV_API size_t hsv_signer_size(const hsv_signer *s);
+/* The public keys, in seed order: nkeys*32 B. */
+HSV_API int hsv_signer_public_keys(const hsv_signer *s, uint8_t *pk_out);
+/* Sign m messages of msg_len bytes each (any length): item i signs
+ * msgs + i*msg_stride with key key_idx[i].  key_idx == NULL: item i uses key
+ * i (m <= nkeys).  msg_stride == 0: one shared message (a committee signing
+ * one QC digest).  An index >= nkeys writes 64 zero bytes and raises no fault
+ * (as hsv_committee_verify answers flags 0).  sig_out: m*64 B, R || s.  Host
+ * buffers, synchronous; m == 0 does nothing.  A failed device self-check (an
+ * [r]B that is not a curve point: corrupted table memory) zeroes that item's
+ * signature and returns HSV_ERR_DEVICE_FAULT. */
+HSV_API int hsv_signer_sign(hsv_signer *s, const uint32_t *key_idx, const uint8_t *msgs, size_t msg_len,
+                            size_t msg_stride, size_t m, uint8_t *sig_out);
+/* Device-resident, stream-ordered form (device = the signer's; no
+ * synchronisation): item i's signature goes to d_sig + i*sig_stride, so
+ * sig_stride 96 with d_sig = records + 32 fills packed pk||R||s vote records.
+ * d_sig and sig_stride must be multiples of 16 (HSV_ERR_ALIGN); d_msg may have
+ * any alignment.  d_fault (optional) as hsv_verify_device_bits (only
+ * d_fault[0] is ever set).  Batches above 2^22 items run as 2^22-item
+ * launches, in order on `stream`. */
+HSV_API int hsv_signer_sign_device(const hsv_signer *s, const uint32_t *d_key_idx, const uint8_t *d_msg, size_t msg_len,
+                                   size_t msg_stride, size_t m, uint8_t *d_sig, size_t sig_stride, uint32_t *d_fault,
+                                   void *stream);
 
 /* Synthesis helper for the corrupted-input mixes (SURVEY 8(d) C3/C4 "mixed-
  * order A"; Appendix A.3 rows 7-8): the key A' = [a]B + [2*torsion+1]T8 (a

@@ -360,4 +360,66 @@ class SignatureService {
 
 }  // namespace crypto
 
+// Batch key derivation and signing on the GPU (hsv_signer_*, hsv.h): the form
+// of generate_keypair / Signature::new a load generator uses.  Not constant
+// time -- never a home for a validator's key.  Owns the signer handle; errors
+// throw crypto::InfrastructureError (there is no CPU fallback).
+namespace hsv {
+
+class Signer {
+ public:
+  // seeds: nkeys * 32 bytes
+  Signer(const uint8_t *seeds, size_t nkeys) {
+    crypto::check_infra(hsv_signer_create(seeds, nkeys, &h_), "hsv_signer_create");
+  }
+  explicit Signer(const std::vector<std::array<uint8_t, 32>> &seeds)
+      : Signer(seeds.empty() ? nullptr : seeds[0].data(), seeds.size()) {}
+  ~Signer() { hsv_signer_destroy(h_); }
+  Signer(const Signer &) = delete;
+  Signer &operator=(const Signer &) = delete;
+  Signer(Signer &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  Signer &operator=(Signer &&o) noexcept {
+    if (this != &o) {
+      hsv_signer_destroy(h_);
+      h_ = o.h_;
+      o.h_ = nullptr;
+    }
+    return *this;
+  }
+
+  size_t size() const { return hsv_signer_size(h_); }
+  std::vector<crypto::PublicKey> public_keys() const {
+    std::vector<uint8_t> raw(size() * 32);
+    crypto::check_infra(hsv_signer_public_keys(h_, raw.data()), "hsv_signer_public_keys");
+    std::vector<crypto::PublicKey> out(size());
+    for (size_t i = 0; i < out.size(); ++i) std::memcpy(out[i].bytes.data(), raw.data() + 32 * i, 32);
+    return out;
+  }
+  // m messages of msg_len bytes at msg_stride (0: one shared message), key
+  // key_idx[i] for item i (nullptr: key i); returns m * 64 bytes, R || s
+  std::vector<uint8_t> sign(const uint32_t *key_idx, const uint8_t *msgs, size_t msg_len, size_t msg_stride,
+                            size_t m) {
+    std::vector<uint8_t> sig(m * 64);
+    crypto::check_infra(hsv_signer_sign(h_, key_idx, msgs, msg_len, msg_stride, m, sig.data()), "hsv_signer_sign");
+    return sig;
+  }
+  // every key signs one digest: the votes of a QC
+  std::vector<uint8_t> sign_all(const crypto::Digest &digest) {
+    return sign(nullptr, digest.bytes.data(), 32, 0, size());
+  }
+  // device-resident, stream-ordered form (hsv_signer_sign_device)
+  void sign_device(const uint32_t *d_key_idx, const uint8_t *d_msg, size_t msg_len, size_t msg_stride, size_t m,
+                   uint8_t *d_sig, size_t sig_stride, uint32_t *d_fault = nullptr, void *stream = nullptr) const {
+    crypto::check_infra(hsv_signer_sign_device(h_, d_key_idx, d_msg, msg_len, msg_stride, m, d_sig, sig_stride,
+                                               d_fault, stream),
+                        "hsv_signer_sign_device");
+  }
+  hsv_signer *handle() const { return h_; }
+
+ private:
+  hsv_signer *h_ = nullptr;
+};
+
+}  // namespace hsv
+
 #endif  // HSV_CRYPTO_HPP_
