@@ -179,6 +179,23 @@ hipError_t hsv_launch_tx_fused(uint32_t grid, const uint8_t *txs, const uint64_t
 hipError_t hsv_launch_verify_tx(int variant, const uint8_t *txs, const uint64_t *offsets, uint64_t tx_size,
                                 uint32_t n, uint8_t *records, uint8_t *flags_out, uint32_t *strict_bits,
                                 const uint32_t *comb_b, uint32_t *fault, hipStream_t stream);
+// Ed25519 over messages of any length (hsv_verify_msgs*): k = SHA-512(R || A
+// || M) over the whole message.  Message i is msgs[offsets[i], offsets[i+1])
+// (offsets != NULL; a decreasing pair gives flags 0) or msg_len bytes at
+// msgs + i * msg_stride; msgs at any alignment, pk / sig and their strides
+// multiples of 16.  Two launches on `stream`: hsv_launch_msg_prep
+// (hsv_msgs.hip: one lane per item hashes its message and writes the SoA
+// prepass record, with k mod l in the b words of a fallback item), then the
+// point pass, which never reads a message.  comb16: the wide comb of B;
+// workspace, fault words and canaries as hsv_launch_verify.
+hipError_t hsv_launch_verify_msgs(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, uint64_t sig_stride,
+                                  const uint8_t *msgs, const uint64_t *offsets, uint64_t msg_len,
+                                  uint64_t msg_stride, uint32_t n, uint8_t *flags_out, uint32_t *strict_bits,
+                                  const uint32_t *comb16, uint32_t *fault, hipStream_t stream);
+hipError_t hsv_launch_msg_prep(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, uint64_t sig_stride,
+                               const uint8_t *msgs, const uint64_t *offsets, uint64_t msg_len, uint64_t msg_stride,
+                               uint32_t n, uint32_t *prep, uint32_t *fb_count, uint32_t *fb_list, int lat_bits,
+                               hipStream_t stream);
 // flags 0 (and STRICT_OK bit cleared) for transactions shorter than 96 bytes
 hipError_t hsv_launch_tx_mask(const uint64_t *offsets, uint32_t n, uint8_t *flags, uint32_t *strict_bits,
                               hipStream_t stream);

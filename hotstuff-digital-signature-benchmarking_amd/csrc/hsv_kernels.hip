@@ -55,7 +55,12 @@ hsv_prep_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const uint8_
 // the full-length path; in the regular range a fallback item's lane computes
 // nothing it stores.  strict_bits is zeroed before the launch and every
 // batch ORs its bits in (a word can receive bits from both ranges).
-template <int WA, int WAVES, int CB>
+// KREC (messages of any length, hsv_launch_verify_msgs): the prepass
+// (hsv_msg_prep_kernel, hsv_msgs.hip) has hashed the whole message, and this
+// pass never touches message bytes (msg is unused): a fallback item's k mod l
+// comes from the b words of its record, and an item the prepass marked
+// kPrepVoid (malformed message range) gets flags 0.
+template <int WA, int WAVES, int CB, bool KREC = false>
 __global__ void __launch_bounds__(kBlock, WAVES)
 hsv_verify_hp_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const uint8_t *__restrict__ sig,
                      uint64_t sig_stride, const uint8_t *__restrict__ msg, uint64_t msg_stride, uint32_t n,
@@ -86,9 +91,30 @@ hsv_verify_hp_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const u
       const uint32_t j = base + lane;
       const bool valid = j < nfb;
       const uint32_t idx = fb_list[valid ? j : base];
-      uint32_t pkw[8], sigw[16], msgw[8];
-      load_triple(pk, pk_stride, sig, sig_stride, msg, msg_stride, idx, pkw, sigw, msgw);
-      const uint32_t f = verify_one_full_comb<WA, false, CB>(pkw, sigw, msgw, comb_b, vt);
+      uint32_t pkw[8], sigw[16];
+      uint32_t f;
+      if constexpr (KREC) {
+        const uint4 *p = reinterpret_cast<const uint4 *>(pk + (uint64_t)idx * pk_stride);
+        const uint4 *s = reinterpret_cast<const uint4 *>(sig + (uint64_t)idx * sig_stride);
+        HSV_UNROLL
+        for (int j = 0; j < 2; ++j) {
+          const uint4 v = p[j];
+          pkw[4 * j] = v.x; pkw[4 * j + 1] = v.y; pkw[4 * j + 2] = v.z; pkw[4 * j + 3] = v.w;
+        }
+        HSV_UNROLL
+        for (int j = 0; j < 4; ++j) {
+          const uint4 v = s[j];
+          sigw[4 * j] = v.x; sigw[4 * j + 1] = v.y; sigw[4 * j + 2] = v.z; sigw[4 * j + 3] = v.w;
+        }
+        sc k;
+        HSV_UNROLL
+        for (int i = 0; i < 8; ++i) k.v[i] = rec[(10ull + (uint64_t)i) * n + idx];
+        f = verify_one_full_comb<WA, false, CB>(pkw, sigw, k, comb_b, vt);
+      } else {
+        uint32_t msgw[8];
+        load_triple(pk, pk_stride, sig, sig_stride, msg, msg_stride, idx, pkw, sigw, msgw);
+        f = verify_one_full_comb<WA, false, CB>(pkw, sigw, msgw, comb_b, vt);
+      }
       bad |= ((f & kFault) ? 1u : 0u) | (canary[slot] != nonce ? 2u : 0u);
       if (valid) {
         if (flags_out) flags_out[idx] = (uint8_t)f;
@@ -134,9 +160,10 @@ hsv_verify_hp_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const u
     const uint32_t f = verify_one_prepped<WA, CB>(pkw, rw, rec + li, n, meta, comb_b, vt);
 #endif
     bad |= ((f & kFault) ? 1u : 0u) | (canary[slot] != nonce ? 2u : 0u);
-    if (own && flags_out) flags_out[idx] = (uint8_t)f;
+    const uint32_t fo = KREC && (meta & kPrepVoid) ? 0u : f;
+    if (own && flags_out) flags_out[idx] = (uint8_t)fo;
     if (strict_bits) {
-      const uint64_t mask = __ballot(own && (f & kStrictOk));
+      const uint64_t mask = __ballot(own && (fo & kStrictOk));
       const uint32_t w = b0 / 32u + lane;
       const uint32_t part = lane ? (uint32_t)(mask >> 32) : (uint32_t)mask;
       if (lane < 2u && w < words && part) atomicOr(&strict_bits[w], part);
@@ -968,30 +995,39 @@ struct TxPrep {
   uint64_t tx_size;
   uint8_t *records;
 };
+// Messages of any length (hsv_launch_verify_msgs): the prepass is
+// hsv_launch_msg_prep, which hashes each whole message, and the point pass is
+// the KREC instantiation, which never reads a message.
+struct MsgPrep {
+  const uint8_t *msgs;
+  const uint64_t *offsets;
+  uint64_t msg_len, msg_stride;
+};
 
 template <int WA, int WAVES, int CB>
 hipError_t launch_hp(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, uint64_t sig_stride,
                      const uint8_t *msg, uint64_t msg_stride, uint32_t n, uint8_t *flags_out,
                      uint32_t *strict_bits, const uint32_t *comb_b, uint32_t *fault, hipStream_t stream,
                      const TxPrep *tx = nullptr, void *ws_in = nullptr, size_t ws_cap = 0,
-                     size_t *ws_need = nullptr) {
-  const void *kern = reinterpret_cast<const void *>(hsv::hsv_verify_hp_kernel<WA, WAVES, CB>);
+                     size_t *ws_need = nullptr, const MsgPrep *mp = nullptr) {
+  const void *kern = mp ? reinterpret_cast<const void *>(hsv::hsv_verify_hp_kernel<WA, WAVES, CB, true>)
+                        : reinterpret_cast<const void *>(hsv::hsv_verify_hp_kernel<WA, WAVES, CB>);
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
   static std::mutex mu;
-  static std::unordered_map<int, std::pair<int, int>> slots_per_dev;  // device -> (blocks per CU, CUs)
+  static std::unordered_map<int, std::pair<int, int>> slots_per_dev;  // device, form -> (blocks per CU, CUs)
   int bpc = 1, cus = 1;
   {
     std::lock_guard<std::mutex> lk(mu);
-    auto it = slots_per_dev.find(dev);
+    auto it = slots_per_dev.find(2 * dev + (mp ? 1 : 0));
     if (it == slots_per_dev.end()) {
       int b = 0, c = 0;
       e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, kern, hsv::kBlock, 0);
       if (e != hipSuccess) return e;
       e = hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
       if (e != hipSuccess) return e;
-      it = slots_per_dev.emplace(dev, std::make_pair(std::max(1, b), std::max(1, c))).first;
+      it = slots_per_dev.emplace(2 * dev + (mp ? 1 : 0), std::make_pair(std::max(1, b), std::max(1, c))).first;
     }
     bpc = it->second.first;
     cus = it->second.second;
@@ -1053,13 +1089,21 @@ hipError_t launch_hp(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, 
     sig = tx->records + 32;
     msg = tx->records + 96;
     pk_stride = sig_stride = msg_stride = 128;
+  } else if (e == hipSuccess && mp) {
+    static_assert(WA == 4, "hsv_launch_msg_prep writes the WA = 4 prepass record");
+    e = hsv_launch_msg_prep(pk, pk_stride, sig, sig_stride, mp->msgs, mp->offsets, mp->msg_len, mp->msg_stride, n,
+                            rec, &ctr->fb_count, fb_list, g_lat_bits.load(), stream);
   } else if (e == hipSuccess) {
     hipLaunchKernelGGL((hsv::hsv_prep_kernel<WA>), dim3(blocks_needed), dim3(hsv::kBlock), 0, stream, pk, pk_stride,
                        sig, sig_stride, msg, msg_stride, n, rec, ctr, fb_list, g_lat_bits.load());
     e = hipGetLastError();
   }
   if (e == hipSuccess) {
-    {
+    if (mp) {
+      hipLaunchKernelGGL((hsv::hsv_verify_hp_kernel<WA, WAVES, CB, true>), dim3(grid), dim3(hsv::kBlock), 0, stream,
+                         pk, pk_stride, sig, sig_stride, nullptr, 0, n, flags_out, strict_bits, vt_ws, comb_b, rec,
+                         ctr, fb_list, canary, next_nonce(), t_inject, fault);
+    } else {
       hipLaunchKernelGGL((hsv::hsv_verify_hp_kernel<WA, WAVES, CB>), dim3(grid), dim3(hsv::kBlock), 0, stream, pk,
                          pk_stride, sig, sig_stride, msg, msg_stride, n, flags_out, strict_bits, vt_ws, comb_b, rec,
                          ctr, fb_list, canary, next_nonce(), t_inject, fault);
@@ -1310,6 +1354,21 @@ extern "C" hipError_t hsv_launch_verify_tx(int variant, const uint8_t *txs, cons
   if (e != hipSuccess) return e;
   return hsv_launch_verify(variant, records, 128, records + 32, 128, records + 96, 128, n, flags_out, strict_bits,
                            comb_b, fault, stream);
+}
+
+// Messages of any length: the message prepass, then the point pass that reads
+// k from the record for fallback items.  Two ordinary launches at every n (no
+// latency form hashes more than 32 bytes).
+extern "C" hipError_t hsv_launch_verify_msgs(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig,
+                                             uint64_t sig_stride, const uint8_t *msgs, const uint64_t *offsets,
+                                             uint64_t msg_len, uint64_t msg_stride, uint32_t n, uint8_t *flags_out,
+                                             uint32_t *strict_bits, const uint32_t *comb16, uint32_t *fault,
+                                             hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  if (!comb16 || !fault) return hipErrorInvalidValue;
+  const MsgPrep mp{msgs, offsets, msg_len, msg_stride};
+  return launch_hp<4, HSV_HP_WAVES, 16>(pk, pk_stride, sig, sig_stride, nullptr, 0, n, flags_out, strict_bits, comb16,
+                                        fault, stream, nullptr, nullptr, 0, nullptr, &mp);
 }
 
 // Variant ids compiled into this library.  The product build carries the

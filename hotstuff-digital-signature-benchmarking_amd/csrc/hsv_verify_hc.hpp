@@ -147,15 +147,14 @@ HSV_INL ge_ext straus_vt(uint32_t d[NV][L], VT &vt, uint32_t flip_last = 0) {
 }
 
 // Full-length path (fallback): [k](-A) by Straus with table 0, [s]B by comb,
-// compared with R as points (dalek's check, verify_one's flags).
+// compared with R as points (dalek's check, verify_one's flags).  This form
+// takes the challenge k = SHA-512(R || A || M) mod l already reduced (the
+// any-length message path reads it from the prepass record, hsv_msgs.hip).
 template <int WA, bool PREFETCH = true, int CB = 8, class VT>
-HSV_INL uint32_t verify_one_full_comb(const uint32_t pk[8], const uint32_t sig[16], const uint32_t msg[8],
+HSV_INL uint32_t verify_one_full_comb(const uint32_t pk[8], const uint32_t sig[16], const sc &k,
                                       const uint32_t *tb, VT &vt) {
   using G = Windows<WA, WA>;
   const uint32_t s_ok = sc_is_canonical(sig + 8);
-  uint32_t h[16];
-  sha512_96(sig, pk, msg, h);
-  const sc k = sc_reduce512(h);
   fe ax, ay;
   const uint32_t a_ok = ge_decompress(pk, ax, ay);
   const uint32_t small_a = a_ok & y_is_small_order(ay);
@@ -169,6 +168,16 @@ HSV_INL uint32_t verify_one_full_comb(const uint32_t pk[8], const uint32_t sig[1
   const uint32_t r_ok = ge_decompress(sig, rx, ry);
   const uint32_t small_r = r_ok & y_is_small_order(ry);
   return flags_byte(s_ok, a_ok, r_ok, small_a, small_r, ge_eq_affine(q, rx, ry)) | fault_bit(a_ok, r_ok, q);
+}
+
+// The same for a 32-byte message, hashed here.
+template <int WA, bool PREFETCH = true, int CB = 8, class VT>
+HSV_INL uint32_t verify_one_full_comb(const uint32_t pk[8], const uint32_t sig[16], const uint32_t msg[8],
+                                      const uint32_t *tb, VT &vt) {
+  uint32_t h[16];
+  sha512_96(sig, pk, msg, h);
+  const sc k = sc_reduce512(h);
+  return verify_one_full_comb<WA, PREFETCH, CB>(pk, sig, k, tb, vt);
 }
 
 template <int WA>
@@ -233,15 +242,21 @@ struct PutPlain {
   static HSV_MEMBER void u32(uint32_t *p, uint32_t v) { *p = v; }
 };
 
+// The prepass after the hash: h = the 64 bytes of SHA-512(R || A || M) as 16
+// little-endian words, s = the signature's scalar.  k mod l, the lattice
+// reduction, the recoding and the record stores.
 // lat_bits: the lattice bound (kLatCombBits; lower values only to exercise the
 // full-length path in tests, hsvi_set_lattice_bits).
-template <int WA, class Put = PutPlain>
-HSV_INL bool prep_scalars(const uint32_t pk[8], const uint32_t sig[16], const uint32_t msg[8], uint32_t *rec,
-                          uint64_t stride, int lat_bits = kLatCombBits) {
+// KREC (the any-length message path, hsv_msgs.hip): the point pass cannot hash
+// the message again, so a fallback item's eight b words -- meaningless for it
+// -- carry k mod l instead; and an item marked `skip` (its message range is
+// malformed) gets the meta word kPrepVoid alone: the point pass answers flags 0.
+constexpr uint32_t kPrepVoid = 8u;
+template <int WA, class Put = PutPlain, bool KREC = false>
+HSV_INL bool prep_from_hash(const uint32_t h[16], const uint32_t s[8], uint32_t *rec, uint64_t stride,
+                            int lat_bits = kLatCombBits, bool skip = false) {
   using G = HalfCombWindows<WA>;
-  const uint32_t s_ok = sc_is_canonical(sig + 8);
-  uint32_t h[16];
-  sha512_96(sig, pk, msg, h);
+  const uint32_t s_ok = sc_is_canonical(s);
   const sc k = sc_reduce512(h);
   const LatOut lat = lattice_reduce(k, lat_bits);
   uint32_t d[5];
@@ -251,12 +266,20 @@ HSV_INL bool prep_scalars(const uint32_t pk[8], const uint32_t sig[16], const ui
   recode_top5<WA, G::NW>(lat.c0, d);
   HSV_UNROLL
   for (int i = 0; i < 5; ++i) Put::u32(rec + (5 + i) * stride, d[i]);
-  const sc b = sc_mul_small(lat.c1, sig + 8);
+  const sc b = sc_mul_small(lat.c1, s);
   HSV_UNROLL
-  for (int i = 0; i < 8; ++i) Put::u32(rec + (10 + i) * stride, b.v[i]);
-  Put::u32(rec + 18 * stride,
-           (s_ok ? kPrepSOk : 0u) | (lat.c0_neg ? kPrepC0Neg : 0u) | (lat.ok ? 0u : kPrepFallback));
-  return !lat.ok;
+  for (int i = 0; i < 8; ++i) Put::u32(rec + (10 + i) * stride, KREC && !lat.ok ? k.v[i] : b.v[i]);
+  const uint32_t meta = (s_ok ? kPrepSOk : 0u) | (lat.c0_neg ? kPrepC0Neg : 0u) | (lat.ok ? 0u : kPrepFallback);
+  Put::u32(rec + 18 * stride, KREC && skip ? kPrepVoid : meta);
+  return !lat.ok && !(KREC && skip);
+}
+
+template <int WA, class Put = PutPlain>
+HSV_INL bool prep_scalars(const uint32_t pk[8], const uint32_t sig[16], const uint32_t msg[8], uint32_t *rec,
+                          uint64_t stride, int lat_bits = kLatCombBits) {
+  uint32_t h[16];
+  sha512_96(sig, pk, msg, h);
+  return prep_from_hash<WA, Put>(h, sig + 8, rec, stride, lat_bits);
 }
 
 // Point pass of a prepped item: the half-size equation of

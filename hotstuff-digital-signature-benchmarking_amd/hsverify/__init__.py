@@ -11,6 +11,7 @@ Layers (top to bottom):
 from ._lib import (A_OK, EQ_OK, PARSE_OK, R_OK, S_OK, SMALL_A, SMALL_R, STRICT_OK,  # noqa: F401
                    HsvLibraryError, LIB_PATH, device_count, load, version)
 from .signer import Signer  # noqa: F401
+from .verifier import verify_msgs, verify_msgs_device  # noqa: F401
 
-__all__ = ["crypto", "verifier", "mempool", "signer", "Signer", "load", "device_count", "version", "HsvLibraryError",
+__all__ = ["crypto", "verifier", "mempool", "signer", "Signer", "verify_msgs", "verify_msgs_device", "load", "device_count", "version", "HsvLibraryError",
            "STRICT_OK", "EQ_OK", "PARSE_OK", "SMALL_A", "SMALL_R", "S_OK", "A_OK", "R_OK"]

@@ -95,6 +95,9 @@ def _declare(lib):
         "hsv_verify_device": (ctypes.c_int, [c_u8p, sz, c_u8p, sz, c_u8p, sz, sz, c_u8p, ctypes.c_void_p]),
         "hsv_verify_device_bits": (ctypes.c_int, [c_u8p, sz, c_u8p, sz, c_u8p, sz, sz, c_u8p, c_u8p,
                                                   ctypes.c_void_p, ctypes.c_void_p]),
+        "hsv_verify_msgs": (ctypes.c_int, [c_u8p, c_u8p, c_u8p, c_u8p, sz, sz, sz, c_u8p]),
+        "hsv_verify_msgs_device": (ctypes.c_int, [c_u8p, sz, c_u8p, sz, c_u8p, c_u8p, sz, sz, sz, c_u8p, c_u8p,
+                                                  ctypes.c_void_p, ctypes.c_void_p]),
         "hsv_verify_transactions": (ctypes.c_int, [c_u8p, c_u8p, sz, c_u8p]),
         "hsv_verify_transactions_fixed": (ctypes.c_int, [c_u8p, sz, sz, c_u8p]),
         "hsv_verify_transactions_device": (ctypes.c_int, [c_u8p, c_u8p, sz, sz, c_u8p, c_u8p, ctypes.c_void_p,
@@ -142,7 +145,7 @@ def _declare(lib):
     optional = set(HOOKS) | {"hsv_host_call_stats", "hsv_host_call_marks", "hsv_pack_threads", "hsv_device_faults",
                              "hsv_sign_mixed_order", "hsv_auto_committee_faults", "hsv_signer_create",
                              "hsv_signer_destroy", "hsv_signer_size", "hsv_signer_public_keys", "hsv_signer_sign",
-                             "hsv_signer_sign_device"}
+                             "hsv_signer_sign_device", "hsv_verify_msgs", "hsv_verify_msgs_device"}
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None) if name in optional else getattr(lib, name)
         if fn is None:

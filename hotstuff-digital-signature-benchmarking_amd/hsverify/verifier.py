@@ -3,6 +3,9 @@
 * :func:`verify_flags`   host numpy arrays -> per-item flag bytes (hsv_verify)
 * :func:`verify_device`  device-resident torch tensors, stream-ordered
                           (hsv_verify_device[_bits]); no synchronisation
+* :func:`verify_msgs`    the same over whole messages of any length (hsv_verify_msgs:
+                          RFC 8032 PureEdDSA, what sign_many and the GPU signer sign)
+* :func:`verify_msgs_device`  its device-tensor, stream-ordered form
 * :func:`sign_many`      bulk RFC 8032 signing on host threads (input synthesis)
 
 Record layout is the reference's byte layout: pk 32 B, sig 64 B (R || s),
@@ -15,6 +18,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from .mempool import pack as pack_msgs  # sequence of bytes -> (u8 buffer, n+1 u64 offsets)
 
 
 def _ptr(a: np.ndarray):
@@ -73,6 +77,66 @@ def verify_device(pk, sig, msg, flags=None, strict_bits=None, stream=None, fault
             ctypes.c_void_p(strict_bits.data_ptr()) if strict_bits is not None else None,
             _fault_ptr(fault), ctypes.c_void_p(stream))
     _lib.check(rc, "hsv_verify_device_bits")
+
+
+def verify_msgs(pk: np.ndarray, sig: np.ndarray, msgs) -> np.ndarray:
+    """Ed25519 over whole messages of any length (hsv_verify_msgs; RFC 8032
+    PureEdDSA, k = SHA-512(R || A || M)): pk (n,32) u8, sig (n,64) u8 and
+    ``msgs`` a sequence of n ``bytes``, or a ``(buffer, offsets)`` pair with
+    message i = buffer[offsets[i]:offsets[i+1]] (n+1 offsets) -> flags (n,) u8.
+    GPU only; decreasing offsets raise HsvLibraryError."""
+    pk = np.ascontiguousarray(pk, dtype=np.uint8).reshape(-1, 32)
+    sig = np.ascontiguousarray(sig, dtype=np.uint8).reshape(-1, 64)
+    n = pk.shape[0]
+    if sig.shape[0] != n:
+        raise ValueError("pk/sig length mismatch")
+    if isinstance(msgs, tuple) and len(msgs) == 2 and not isinstance(msgs[0], (bytes, bytearray, memoryview)):
+        buf = np.ascontiguousarray(msgs[0], dtype=np.uint8).reshape(-1)
+        offsets = np.ascontiguousarray(msgs[1], dtype=np.uint64).reshape(-1)
+    else:
+        buf, offsets = pack_msgs(msgs)
+    if offsets.size != n + 1:
+        raise ValueError("one message per item (n + 1 offsets)")
+    if n and buf.size < int(offsets.max()):
+        raise ValueError("offsets run past the buffer")
+    out = np.zeros(n, dtype=np.uint8)
+    if n == 0:
+        return out
+    lib = _lib.load()
+    _lib.check(lib.hsv_verify_msgs(_ptr(pk), _ptr(sig), _ptr(buf) if buf.size else None, _ptr(offsets), 0, 0, n,
+                                   _ptr(out)), "hsv_verify_msgs")
+    return out
+
+
+def verify_msgs_device(pk, sig, msgs, offsets=None, msg_len: int = 0, msg_stride: int | None = None,
+                       flags=None, strict_bits=None, stream=None, fault=None) -> None:
+    """Enqueue verification over whole messages of device tensors (uint8):
+    pk (n,32) and sig (n,64) rows at strides that are multiples of 16; ``msgs``
+    the message bytes at any alignment, ``offsets`` an int64 tensor of n+1 byte
+    offsets into it, or None for ``msg_len`` bytes per item at ``msg_stride``
+    (default msg_len; 0 = one shared message).  Outputs ``flags`` (n,) uint8
+    and/or ``strict_bits`` (ceil(n/32),) int32; ``fault`` as in
+    :func:`verify_device`.  No synchronisation (hsv_verify_msgs_device)."""
+    import torch
+
+    n = pk.shape[0]
+    for t in (sig, msgs, offsets, flags, strict_bits, fault):
+        if t is not None and t.device != pk.device:
+            raise ValueError(f"all tensors must live on {pk.device}, got {t.device}")
+    if msg_stride is None:
+        msg_stride = msg_len
+    with torch.cuda.device(pk.device):  # the library launches on the inputs' device
+        if stream is None:
+            stream = torch.cuda.current_stream(pk.device).cuda_stream
+        lib = _lib.load()
+        rc = lib.hsv_verify_msgs_device(
+            ctypes.c_void_p(pk.data_ptr()), pk.stride(0), ctypes.c_void_p(sig.data_ptr()), sig.stride(0),
+            ctypes.c_void_p(msgs.data_ptr()) if msgs is not None else None,
+            ctypes.c_void_p(offsets.data_ptr()) if offsets is not None else None, msg_len, msg_stride, n,
+            ctypes.c_void_p(flags.data_ptr()) if flags is not None else None,
+            ctypes.c_void_p(strict_bits.data_ptr()) if strict_bits is not None else None,
+            _fault_ptr(fault), ctypes.c_void_p(stream))
+    _lib.check(rc, "hsv_verify_msgs_device")
 
 
 def _fault_ptr(fault):

@@ -8,6 +8,8 @@
  *   crypto::Signature::verify_batch  crypto/src/lib.rs:210-223  -> hsv_verify_batch
  *                                                                   hsv_verify_batch_packed
  *   (batched strict API)                     -> hsv_verify
+ *   (the same over whole messages of any length, RFC 8032 5.1.7) -> hsv_verify_msgs,
+ *                                                                   hsv_verify_msgs_device
  *   crypto::Signature::new           crypto/src/lib.rs:185-191  -> hsv_sign, hsv_signer_sign*
  *   crypto::generate_keypair         crypto/src/lib.rs:167-175  -> hsv_public_key, hsv_signer_create
  *   mempool transaction check  mempool/src/batch_maker.rs:79-85 -> hsv_verify_transactions*
@@ -197,6 +199,40 @@ HSV_API int hsv_verify_device(const uint8_t *d_pk, size_t pk_stride, const uint8
 HSV_API int hsv_verify_device_bits(const uint8_t *d_pk, size_t pk_stride, const uint8_t *d_sig,
                            size_t sig_stride, const uint8_t *d_msg, size_t msg_stride, size_t n,
                            uint8_t *d_flags, uint32_t *d_strict_bits, uint32_t *d_fault, void *stream);
+
+/* ---- verification over messages of any length ----------------------------- */
+/* Ed25519 over messages of any length: flags as hsv_verify, with
+ * k = SHA-512(R || A || M) over the whole message M (RFC 8032 5.1.7, dalek
+ * verify_strict's rules for everything else).  This is the verifying half of
+ * hsv_signer_sign* and hsv_sign_many; a mempool transaction
+ * (hsv_verify_transactions*) is a different scheme, signed over
+ * SHA-512(message)[..32].
+ * offsets != NULL: message i is msgs[offsets[i] .. offsets[i+1]) (n+1 entries).
+ * offsets == NULL: message i is msg_len bytes at msgs + i*msg_stride
+ *                  (msg_stride 0: one shared message).
+ * A message may be empty.  msgs may have any alignment.
+ * Host form: synchronous, on the bound or current device; n == 0 does
+ * nothing.  Decreasing offsets, or a NULL msgs when any message is non-empty,
+ * return HSV_ERR_INVALID_ARG; a failed device self-check returns
+ * HSV_ERR_DEVICE_FAULT.  There is no CPU fallback (HSV_ERR_NO_DEVICE without a
+ * GPU).  Plain staged copies on one device: this call is neither pipelined
+ * nor sharded across GPUs. */
+HSV_API int hsv_verify_msgs(const uint8_t *pk, const uint8_t *sig, const uint8_t *msgs,
+                            const uint64_t *offsets, size_t msg_len, size_t msg_stride,
+                            size_t n, uint8_t *flags_out);
+/* Device-resident, stream-ordered form; never synchronises.  d_pk, d_sig and
+ * their strides must be multiples of 16 (HSV_ERR_ALIGN), as in
+ * hsv_verify_device; d_msgs, msg_stride and the offsets (relative to d_msgs)
+ * may have any alignment.  d_flags, d_strict_bits and d_fault as
+ * hsv_verify_device_bits (either output may be NULL, not both).  An item whose
+ * offsets decrease gets flags 0; its neighbours are unaffected.  Batches above
+ * 2^22 items run as 2^22-item launches, in order on `stream`.  Every batch
+ * size takes the same two launches (message prepass, point pass): the latency
+ * forms of hsv_verify_device hash a 32-byte message and are not used here. */
+HSV_API int hsv_verify_msgs_device(const uint8_t *d_pk, size_t pk_stride, const uint8_t *d_sig,
+                                   size_t sig_stride, const uint8_t *d_msgs, const uint64_t *d_offsets,
+                                   size_t msg_len, size_t msg_stride, size_t n, uint8_t *d_flags,
+                                   uint32_t *d_strict_bits, uint32_t *d_fault, void *stream);
 
 /* Self-check results of the device-resident calls on `device` (-1: every
  * device) that ran without a d_fault of their own, since the last clear.

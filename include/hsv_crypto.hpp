@@ -306,6 +306,28 @@ class Signature {
     check_infra(rc, "hsv_verify_batch_packed");
     return rc == 1 ? Result::ok() : Result::err();
   }
+
+  // Signatures over whole messages of any length (hsv_verify_msgs; RFC 8032
+  // PureEdDSA, what hsv::Signer::sign produces): item i is items[i] over
+  // msgs[i].  Returns the per-item HSV_* flag bytes (HSV_STRICT_OK = dalek's
+  // verify_strict Ok).  GPU only: no host route and no fallback.
+  static std::vector<uint8_t> verify_msgs(const std::vector<std::pair<PublicKey, Signature>> &items,
+                                          const std::vector<std::vector<uint8_t>> &msgs) {
+    if (msgs.size() != items.size()) throw std::invalid_argument("verify_msgs: one message per item");
+    const size_t n = items.size();
+    std::vector<uint8_t> pk(n * 32), sig(n * 64), buf, flags(n);
+    std::vector<uint64_t> offsets(n + 1, 0);
+    for (size_t i = 0; i < n; ++i) {
+      std::memcpy(pk.data() + 32 * i, items[i].first.bytes.data(), 32);
+      std::memcpy(sig.data() + 64 * i, items[i].second.part1.data(), 32);
+      std::memcpy(sig.data() + 64 * i + 32, items[i].second.part2.data(), 32);
+      buf.insert(buf.end(), msgs[i].begin(), msgs[i].end());
+      offsets[i + 1] = buf.size();
+    }
+    check_infra(hsv_verify_msgs(pk.data(), sig.data(), buf.data(), offsets.data(), 0, 0, n, flags.data()),
+                "hsv_verify_msgs");
+    return flags;
+  }
 };
 
 // SignatureService (lib.rs:229-254): a worker owns the secret key and answers
