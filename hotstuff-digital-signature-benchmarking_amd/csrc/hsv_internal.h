@@ -218,6 +218,21 @@ hipError_t hsv_launch_keygen(const uint8_t *seeds, uint32_t n, uint8_t *keys, co
 hipError_t hsv_launch_sign(const uint8_t *keys, uint32_t nkeys, const uint32_t *key_idx, const uint8_t *msg,
                            uint64_t msg_len, uint64_t msg_stride, uint32_t m, uint8_t *sig, uint64_t sig_stride,
                            const uint32_t *comb16, uint32_t *fault, hipStream_t stream);
+// Mempool transactions signed in place (hsv_txsign.hpp): pk || R || s into the
+// last 96 bytes of transaction i (offsets[i]..offsets[i+1] of txs, or fixed
+// tx_size when offsets is NULL; any alignment), over SHA-512(message)[..32].
+// Two launches: hsv_launch_tx_digest (hsv_txsign.hip; dig: m * 32 B, 16-byte
+// aligned, status: m words) and the signing launch.  A transaction shorter
+// than 96 bytes or with decreasing offsets is left untouched.
+hipError_t hsv_launch_tx_sign(const uint8_t *keys, uint32_t nkeys, const uint32_t *key_idx, uint8_t *txs,
+                              const uint64_t *offsets, uint64_t tx_size, uint32_t m, const uint32_t *comb16,
+                              uint32_t *fault, hipStream_t stream);
+hipError_t hsv_launch_tx_digest(const uint8_t *txs, const uint64_t *offsets, uint64_t tx_size,
+                                const uint32_t *key_idx, uint32_t nkeys, uint32_t n, uint8_t *dig, uint32_t *status,
+                                hipStream_t stream);
+// Items per launch of hsv_signer_sign_transactions* (tests; 0 = the default
+// 2^22); previous value.
+size_t hsvi_set_tx_sign_chunk(size_t items);
 // Items per lane (G) of the following signer launches: one of the built
 // values (1, 2, 4, 8, 16), 0 = the product's; previous value or -1.
 int hsvi_set_signer_group(int g);

@@ -306,15 +306,28 @@ struct SignArgs {
   const uint8_t *msg;       // item i's message at msg + i * msg_stride (0: one shared message), any alignment
   uint64_t msg_len, msg_stride;
   uint64_t m;
-  uint8_t *sig;             // item i's R || s at sig + i * sig_stride, 16-byte aligned
-  uint64_t sig_stride;
+  uint8_t *sig;             // item i's R || s at sig + i * sig_stride, 16-byte aligned (SignSlotIo; unused by
+  uint64_t sig_stride;      // the transaction signer, whose TxSignIo knows where the tails are)
   const uint32_t *table;    // comb of B (WB-bit digits)
   uint32_t inject, inject_item;  // tests (host build): corrupt the table entry item inject_item reads
 };
 
+// Where sign_lane takes an item's slot status from and where the item's
+// output goes.  This one is hsv_signer_sign*'s: every item of the batch is
+// live, and R || s goes to the item's aligned 64-byte slot.  The transaction
+// signer's is TxSignIo (hsv_txsign.hpp).
+struct SignSlotIo {
+  // kSlotOk (sign), kSlotZero (zero output) or kSlotDead (the item is skipped: nothing is written)
+  HSV_MEMBER uint32_t slot(const SignArgs &a, uint64_t, uint32_t ki) const { return ki < a.nkeys ? kSlotOk : kSlotZero; }
+  // status: kSlotOk (sigw = R || s), kSlotZero or kSlotFault (sigw = 0)
+  HSV_MEMBER void store(const SignArgs &a, uint64_t i, uint32_t, const uint32_t sigw[16]) const {
+    sign_store16<16>(a.sig + i * a.sig_stride, sigw);
+  }
+};
+
 // FAST: msg_len == 32 (the Digest): both hashes are one block each.
-template <int WB, int G, bool FAST, class Store>
-HSV_INL uint32_t sign_lane(const SignArgs &a, uint64_t first, uint32_t step, Store &st) {
+template <int WB, int G, bool FAST, class Store, class Io = SignSlotIo>
+HSV_INL uint32_t sign_lane(const SignArgs &a, uint64_t first, uint32_t step, Store &st, const Io &io = Io()) {
   fe pp = fe_small(1);
   uint32_t bad = 0;
   HSV_NOUNROLL
@@ -323,8 +336,8 @@ HSV_INL uint32_t sign_lane(const SignArgs &a, uint64_t first, uint32_t step, Sto
     uint32_t status = kSlotDead;
     if (i < a.m) {
       const uint32_t ki = a.key_idx ? a.key_idx[i] : (uint32_t)i;
-      status = kSlotZero;
-      if (ki < a.nkeys) {
+      status = io.slot(a, i, ki);
+      if (status == kSlotOk) {
         const uint8_t *mp = a.msg + i * a.msg_stride;
         uint32_t in[16], h[16];
         sign_load16<8>(a.keys + (uint64_t)ki * kSignKeyBytes + 32, in);  // prefix
@@ -385,7 +398,7 @@ HSV_INL uint32_t sign_lane(const SignArgs &a, uint64_t first, uint32_t step, Sto
         }
       }
     }
-    sign_store16<16>(a.sig + i * a.sig_stride, sigw);
+    io.store(a, i, status, sigw);
   }
   return bad;
 }

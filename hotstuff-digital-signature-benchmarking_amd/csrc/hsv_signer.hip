@@ -2,8 +2,12 @@
 //
 //  hsv_keygen_kernel  seeds -> 96-byte expanded key records a | prefix | pk
 //  hsv_sign_kernel    (key record, message) -> R || s
+//  hsv_tx_sign_kernel (key record, digest of a transaction's message) -> pk || R || s
+//                     at the end of the transaction, at any byte address
+//                     (hsv_txsign.hpp; its digests come from hsv_tx_digest_kernel,
+//                     hsv_txsign.hip, the launch before it)
 //
-// Both run csrc/hsv_sign_core.hpp's lane functions on a plain grid: a wave
+// All run csrc/hsv_sign_core.hpp's lane functions on a plain grid: a wave
 // takes 64 * G consecutive items, lane l the items base + g * 64 + l (g < G),
 // so every load and store of a wave is coalesced.  The state an item keeps
 // between the two phases (its point, the prefix product before it, r: 49
@@ -17,6 +21,7 @@
 
 #include "hsv_internal.h"
 #include "hsv_sign_core.hpp"
+#include "hsv_txsign.hpp"
 
 namespace hsv {
 
@@ -52,6 +57,19 @@ __global__ void __launch_bounds__(kSignBlock) hsv_sign_kernel(SignArgs a, uint32
   if (sign_lane<16, G, FAST>(a, base + lane, 64u, st)) fault[0] = 1u;
 }
 
+// The one-block fast path over the digests of the launch workspace (a.msg,
+// stride 32); status and store through TxSignIo.
+template <int G>
+__global__ void __launch_bounds__(kSignBlock) hsv_tx_sign_kernel(SignArgs a, TxSignIo io, uint32_t *__restrict__ ws,
+                                                                 uint32_t *__restrict__ fault) {
+  const uint32_t wave = blockIdx.x * (kSignBlock / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  const uint64_t base = (uint64_t)wave * 64u * G;
+  if (base >= a.m) return;  // the whole wave is past the end
+  LaneStore st{ws + (uint64_t)wave * G * kSignWsWords * 64u + lane};
+  a.inject = kInjectNone;
+  if (sign_lane<16, G, true>(a, base + lane, 64u, st, io)) fault[0] = 1u;
+}
+
 }  // namespace hsv
 
 namespace {
@@ -80,6 +98,12 @@ void launch_sign(const hsv::SignArgs &a, uint32_t blocks, uint32_t *ws, uint32_t
     hipLaunchKernelGGL((hsv::hsv_sign_kernel<G, true>), dim3(blocks), dim3(hsv::kSignBlock), 0, stream, a, ws, fault);
   else
     hipLaunchKernelGGL((hsv::hsv_sign_kernel<G, false>), dim3(blocks), dim3(hsv::kSignBlock), 0, stream, a, ws, fault);
+}
+
+template <int G>
+void launch_tx_sign(const hsv::SignArgs &a, const hsv::TxSignIo &io, uint32_t blocks, uint32_t *ws, uint32_t *fault,
+                    hipStream_t stream) {
+  hipLaunchKernelGGL((hsv::hsv_tx_sign_kernel<G>), dim3(blocks), dim3(hsv::kSignBlock), 0, stream, a, io, ws, fault);
 }
 
 }  // namespace
@@ -139,5 +163,39 @@ extern "C" hipError_t hsv_launch_sign(const uint8_t *keys, uint32_t nkeys, const
   }
   e = hipGetLastError();
   const hipError_t ef = hipFreeAsync(ws, stream);
+  return e != hipSuccess ? e : ef;
+}
+
+// Two launches on `stream`: the digests and slot statuses of the m transactions
+// (hsv_txsign.hip) into the workspace, then the signing launch over them.
+extern "C" hipError_t hsv_launch_tx_sign(const uint8_t *keys, uint32_t nkeys, const uint32_t *key_idx, uint8_t *txs,
+                                         const uint64_t *offsets, uint64_t tx_size, uint32_t m,
+                                         const uint32_t *comb16, uint32_t *fault, hipStream_t stream) {
+  if (m == 0) return hipSuccess;
+  if (m > (1u << 22)) return hipErrorInvalidValue;
+  const int group = g_group.load();
+  const Grid gr = grid_for(m, group);
+  // the signing workspace | m digests of 32 B | m status words
+  const size_t off_dig = gr.ws_bytes, off_status = off_dig + (size_t)m * 32;
+  void *blk = nullptr;
+  hipError_t e = hsv_ws_malloc(&blk, off_status + (size_t)m * 4, stream);
+  if (e != hipSuccess) return e;
+  uint8_t *d = static_cast<uint8_t *>(blk);
+  uint32_t *status = reinterpret_cast<uint32_t *>(d + off_status);
+  e = hsv_launch_tx_digest(txs, offsets, tx_size, key_idx, nkeys, m, d + off_dig, status, stream);
+  if (e == hipSuccess) {
+    const hsv::SignArgs a{keys, nkeys, key_idx, d + off_dig, 32, 32, m, nullptr, 0, comb16, hsv::kInjectNone, 0u};
+    const hsv::TxSignIo io{status, txs, offsets, tx_size};
+    uint32_t *w = static_cast<uint32_t *>(blk);
+    switch (group) {
+      case 1: launch_tx_sign<1>(a, io, gr.blocks, w, fault, stream); break;
+      case 2: launch_tx_sign<2>(a, io, gr.blocks, w, fault, stream); break;
+      case 4: launch_tx_sign<4>(a, io, gr.blocks, w, fault, stream); break;
+      case 8: launch_tx_sign<8>(a, io, gr.blocks, w, fault, stream); break;
+      default: launch_tx_sign<16>(a, io, gr.blocks, w, fault, stream); break;
+    }
+    e = hipGetLastError();
+  }
+  const hipError_t ef = hipFreeAsync(blk, stream);
   return e != hipSuccess ? e : ef;
 }

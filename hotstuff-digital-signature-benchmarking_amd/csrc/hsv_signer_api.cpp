@@ -5,6 +5,9 @@
 // expanded record a | prefix | pk per key (hsv_keygen_kernel) and signs from
 // them with hsv_sign_kernel (csrc/hsv_signer.hip).  There is no CPU fallback:
 // hsv_sign_many is the host signer.
+// hsv_signer_sign_transactions* is the signing mirror of hsv_verify_transactions*
+// (the client's half of mempool/src/batch_maker.rs:79-85): pk || R || s into the
+// last 96 bytes of every transaction, in place (csrc/hsv_txsign.hpp).
 #include <algorithm>
 #include <memory>
 #include <string>
@@ -47,7 +50,32 @@ int sign_args_ok(const hsv_signer *s, const uint32_t *key_idx, const void *msg, 
   return HSV_OK;
 }
 
+// ---- transactions (hsv_signer_sign_transactions*) -------------------------------
+constexpr size_t kTxSignChunkBytes = size_t(1) << 29;  // transaction bytes staged per launch of the host form
+std::atomic<size_t> g_tx_chunk{kChunk};                // items per launch (hsvi_set_tx_sign_chunk: tests)
+
+// launches of at most g_tx_chunk items, one after the other on `stream`;
+// d_offsets are relative to d_txs, so a chunk only moves along the offsets
+hipError_t tx_sign_chunks(const hsv_signer &s, const uint32_t *d_key_idx, uint8_t *d_txs, const uint64_t *d_offsets,
+                          size_t tx_size, size_t n, const uint32_t *comb16, uint32_t *fault, hipStream_t stream) {
+  const size_t per = g_tx_chunk.load();
+  hipError_t e = hipSuccess;
+  for (size_t base = 0; base < n && e == hipSuccess; base += per) {
+    const size_t k = std::min(per, n - base);
+    // key_idx == NULL: item i uses key i (n <= s.n), so a chunk's records start at its base
+    const size_t kb = std::min(base, s.n);
+    e = hsv_launch_tx_sign(s.d_keys + (d_key_idx ? 0 : kb * 96), (uint32_t)(d_key_idx ? s.n : s.n - kb),
+                           d_key_idx ? d_key_idx + base : nullptr, d_offsets ? d_txs : d_txs + base * tx_size,
+                           d_offsets ? d_offsets + base : nullptr, tx_size, (uint32_t)k, comb16, fault, stream);
+  }
+  return e;
+}
+
 }  // namespace
+
+extern "C" size_t hsvi_set_tx_sign_chunk(size_t items) {
+  return g_tx_chunk.exchange(items == 0 || items > kChunk ? kChunk : items);
+}
 
 extern "C" {
 
@@ -188,6 +216,129 @@ int hsv_signer_sign(hsv_signer *s, const uint32_t *key_idx, const uint8_t *msgs,
   if (e == hipSuccess) e = es;
   if (e != hipSuccess) return hip_fail("hsv_signer_sign", e);
   return check_faults(words, "hsv_signer_sign");
+}
+
+int hsv_signer_sign_transactions_device(const hsv_signer *s, const uint32_t *d_key_idx, uint8_t *d_txs,
+                                        const uint64_t *d_offsets, size_t tx_size, size_t n, uint32_t *d_fault,
+                                        void *stream) {
+  if (n == 0) return HSV_OK;
+  if (!s || !d_txs) return fail(HSV_ERR_INVALID_ARG, "null argument");
+  if (reinterpret_cast<uintptr_t>(d_key_idx) & 3u) return fail(HSV_ERR_ALIGN, "d_key_idx must be 4-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_offsets) & 7u) return fail(HSV_ERR_ALIGN, "d_offsets must be 8-byte aligned");
+  if (!d_offsets && tx_size < 96) return fail(HSV_ERR_INVALID_ARG, "transactions are shorter than 96 bytes");
+  if (n > 0xffffffffu) return fail(HSV_ERR_INVALID_ARG, "batch too large");
+  int rc = ensure_init();
+  if (rc != HSV_OK) return rc;
+  if (!d_key_idx && n > s->n) return fail(HSV_ERR_INVALID_ARG, "more items than keys and no key_idx");
+  // the buffers and the stream are on the signer's device
+  const int pd = pointer_device(d_txs);
+  if (pd >= 0 && pd != s->device)
+    return fail(HSV_ERR_INVALID_ARG, "buffers live on device " + std::to_string(pd) + ", the signer on device " +
+                                         std::to_string(s->device));
+  if (stream) {
+    int sd = -1;
+    if (hipStreamGetDevice(reinterpret_cast<hipStream_t>(stream), &sd) == hipSuccess && sd >= 0 && sd != s->device)
+      return fail(HSV_ERR_INVALID_ARG, "the stream belongs to device " + std::to_string(sd) +
+                                           ", the signer to device " + std::to_string(s->device));
+    (void)hipGetLastError();
+  }
+  DevCtx &c = ctx(s->device);
+  DeviceGuard guard(c.device);
+  if (guard.status() != hipSuccess) return hip_fail("hipSetDevice", guard.status());
+  rc = ensure_btable16(c);  // the B table is rebuilt if hsv_shutdown released it
+  if (rc != HSV_OK) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  uint32_t *fault = nullptr;
+  rc = call_fault_words(c, d_fault, st, &fault);
+  if (rc != HSV_OK) return rc;
+  const hipError_t e = tx_sign_chunks(*s, d_key_idx, d_txs, d_offsets, tx_size, n, c.d_btable16, fault, st);
+  return e == hipSuccess ? HSV_OK : hip_fail("transaction sign launch", e);
+}
+
+int hsv_signer_sign_transactions(hsv_signer *s, const uint32_t *key_idx, uint8_t *txs, const uint64_t *offsets,
+                                 size_t tx_size, size_t n) {
+  if (n == 0) return HSV_OK;
+  if (!s || !txs) return fail(HSV_ERR_INVALID_ARG, "null argument");
+  if (n > 0xffffffffu) return fail(HSV_ERR_INVALID_ARG, "batch too large");
+  if (offsets) {  // the length check of hsv_verify_transactions
+    for (size_t i = 0; i < n; ++i)
+      if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] < 96)
+        return fail(HSV_ERR_INVALID_ARG, "transaction " + std::to_string(i) + " is shorter than 96 bytes");
+  } else if (tx_size < 96) {
+    return fail(HSV_ERR_INVALID_ARG, "transactions are shorter than 96 bytes");
+  }
+  int rc = ensure_init();
+  if (rc != HSV_OK) return rc;
+  if (!key_idx && n > s->n) return fail(HSV_ERR_INVALID_ARG, "more items than keys and no key_idx");
+  DevCtx &c = ctx(s->device);
+  DeviceGuard guard(c.device);
+  if (guard.status() != hipSuccess) return hip_fail("hipSetDevice", guard.status());
+  rc = ensure_btable16(c);
+  if (rc != HSV_OK) return rc;
+  SlotLease lease(c);
+  Slot &slot = lease.slot();
+  rc = slot_prepare(slot, 0, 0);
+  if (rc != HSV_OK) return rc;
+  hipStream_t st = slot.stream;
+  const size_t per_launch = g_tx_chunk.load();
+  std::vector<uint64_t> rel;  // a chunk's offsets, relative to its first byte
+  std::vector<uint8_t> back;  // a ragged chunk as the device left it
+  for (size_t a = 0; a < n;) {
+    // items [a, b): at most one launch, and at most kTxSignChunkBytes unless one transaction is longer
+    size_t b = a + 1;
+    if (!offsets) {
+      b = std::min(n, a + std::min(per_launch, std::max<size_t>(1, kTxSignChunkBytes / tx_size)));
+    } else {
+      while (b < n && b - a < per_launch && offsets[b + 1] - offsets[a] <= kTxSignChunkBytes) ++b;
+    }
+    const size_t m = b - a;
+    const size_t first = offsets ? (size_t)offsets[a] : a * tx_size;
+    const size_t bytes = offsets ? (size_t)(offsets[b] - offsets[a]) : m * tx_size;
+    // one stream-ordered block from the library pool: fault words | key indices | offsets | transactions
+    const size_t off_idx = kAlign, off_offs = off_idx + round_up(key_idx ? m * 4 : 0, kAlign);
+    const size_t off_tx = off_offs + round_up(offsets ? (m + 1) * 8 : 0, kAlign);
+    void *blk = nullptr;
+    hipError_t e = hsv_ws_malloc(&blk, off_tx + bytes + kAlign, st);
+    if (e != hipSuccess) return hip_fail("allocating the transaction signing buffers", e);
+    uint8_t *d = static_cast<uint8_t *>(blk);
+    uint32_t *d_fault = reinterpret_cast<uint32_t *>(d);
+    uint32_t *d_idx = key_idx ? reinterpret_cast<uint32_t *>(d + off_idx) : nullptr;
+    uint64_t *d_offs = offsets ? reinterpret_cast<uint64_t *>(d + off_offs) : nullptr;
+    uint8_t words[kFaultBytes] = {0};
+    e = hipMemsetAsync(d_fault, 0, kFaultBytes, st);
+    if (e == hipSuccess && key_idx) e = hipMemcpyAsync(d_idx, key_idx + a, m * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && offsets) {
+      rel.resize(m + 1);
+      for (size_t k = 0; k <= m; ++k) rel[k] = offsets[a + k] - offsets[a];
+      e = hipMemcpyAsync(d_offs, rel.data(), (m + 1) * 8, hipMemcpyHostToDevice, st);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(d + off_tx, txs + first, bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+      const size_t kb = std::min(a, s->n);  // key_idx == NULL: item i uses key i
+      e = hsv_launch_tx_sign(s->d_keys + (key_idx ? 0 : kb * 96), (uint32_t)(key_idx ? s->n : s->n - kb), d_idx,
+                             d + off_tx, d_offs, tx_size, (uint32_t)m, c.d_btable16, d_fault, st);
+    }
+    // only the tails come back: the caller's message bytes are never written
+    if (e == hipSuccess && !offsets)
+      e = hipMemcpy2DAsync(txs + first + (tx_size - 96), tx_size, d + off_tx + (tx_size - 96), tx_size, 96, m,
+                           hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && offsets) {
+      back.resize(bytes);
+      e = hipMemcpyAsync(back.data(), d + off_tx, bytes, hipMemcpyDeviceToHost, st);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(words, d_fault, kFaultBytes, hipMemcpyDeviceToHost, st);
+    const hipError_t ef = hipFreeAsync(blk, st);
+    const hipError_t es = hipStreamSynchronize(st);  // nothing of this call stays in flight
+    if (e == hipSuccess) e = ef;
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return hip_fail("hsv_signer_sign_transactions", e);
+    if (offsets)
+      for (size_t k = 0; k < m; ++k) std::memcpy(txs + first + rel[k + 1] - 96, back.data() + rel[k + 1] - 96, 96);
+    rc = check_faults(words, "hsv_signer_sign_transactions");
+    if (rc != HSV_OK) return rc;
+    a = b;
+  }
+  return HSV_OK;
 }
 
 }  // extern "C"

@@ -76,5 +76,6 @@ int hsv_test_tx_records(const uint8_t *d_txs, const uint64_t *d_offsets, size_t 
   return e == hipSuccess ? HSV_OK : HSV_ERR_HIP;
 }
 int hsv_test_signer_group(int g) { return hsvi_set_signer_group(g); }
+size_t hsv_test_tx_sign_chunk(size_t items) { return hsvi_set_tx_sign_chunk(items); }
 
 }  // extern "C"

@@ -80,6 +80,10 @@ HSV_API int hsv_test_tx_records(const uint8_t *d_txs, const uint64_t *d_offsets,
  * restores the product's.  Returns the previous value, or -1 for a value that
  * is not built. */
 HSV_API int hsv_test_signer_group(int g);
+/* Tests: items per launch of hsv_signer_sign_transactions* (the product's is
+ * 2^22), so that a batch of a few hundred transactions crosses a launch
+ * boundary.  0 restores the product's.  Returns the previous value. */
+HSV_API size_t hsv_test_tx_sign_chunk(size_t items);
 
 #ifdef __cplusplus
 }

@@ -28,7 +28,8 @@ HOOKS = ("hsv_test_inject_fault", "hsv_test_inject_mode", "hsv_test_corrupt_auto
          "hsv_test_lanesplit_check", "hsv_set_lattice_bits", "hsv_set_variant", "hsv_variant_list",
          "hsv_variant_available", "hsv_num_variants", "hsv_set_virtual_shards", "hsv_test_pipe_nocopy",
          "hsv_test_resident_counts", "hsv_test_resident_post_bad", "hsv_test_tx_records",
-         "hsv_test_pipe_schedule", "hsv_test_numa_plan", "hsv_test_pinned_thread_cpus", "hsv_test_signer_group")
+         "hsv_test_pipe_schedule", "hsv_test_numa_plan", "hsv_test_pinned_thread_cpus", "hsv_test_signer_group",
+         "hsv_test_tx_sign_chunk")
 
 # flag bits (include/hsv.h)
 STRICT_OK = 0x01
@@ -139,13 +140,18 @@ def _declare(lib):
         "hsv_signer_sign": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u8p, sz, sz, sz, c_u8p]),
         "hsv_signer_sign_device": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u8p, sz, sz, sz, c_u8p, sz,
                                                   ctypes.c_void_p, ctypes.c_void_p]),
+        "hsv_signer_sign_transactions": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u8p, c_u8p, sz, sz]),
+        "hsv_signer_sign_transactions_device": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u8p, c_u8p, sz, sz,
+                                                               ctypes.c_void_p, ctypes.c_void_p]),
         "hsv_test_signer_group": (ctypes.c_int, [ctypes.c_int]),
+        "hsv_test_tx_sign_chunk": (sz, [sz]),
     }
     # hooks (libhsv_test.so only) and entry points absent from older A/B builds (tools/ab_probe.py)
     optional = set(HOOKS) | {"hsv_host_call_stats", "hsv_host_call_marks", "hsv_pack_threads", "hsv_device_faults",
                              "hsv_sign_mixed_order", "hsv_auto_committee_faults", "hsv_signer_create",
                              "hsv_signer_destroy", "hsv_signer_size", "hsv_signer_public_keys", "hsv_signer_sign",
-                             "hsv_signer_sign_device", "hsv_verify_msgs", "hsv_verify_msgs_device"}
+                             "hsv_signer_sign_device", "hsv_verify_msgs", "hsv_verify_msgs_device",
+                             "hsv_signer_sign_transactions", "hsv_signer_sign_transactions_device"}
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None) if name in optional else getattr(lib, name)
         if fn is None:

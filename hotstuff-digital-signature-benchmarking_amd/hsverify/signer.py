@@ -4,7 +4,9 @@ The GPU form of the reference's ``generate_keypair`` and ``Signature::new``
 (crypto/src/lib.rs:167-175, 185-191) for load generators and input synthesis:
 ``Signer(seeds)`` expands the seeds once into key records in HBM, and
 ``sign`` / ``sign_device`` produce RFC 8032 signatures bit-exact with
-``verifier.sign_many``.  Not constant time (table lookups are indexed by
+``verifier.sign_many``; ``sign_transactions`` / ``sign_transactions_device``
+fill in ``pk || R || s`` at the end of mempool transactions, the signing mirror
+of ``mempool.verify_transactions*``.  Not constant time (table lookups are indexed by
 secret digits): never use it to hold a validator's key.  There is no CPU
 fallback; without a GPU the constructor raises.
 """
@@ -88,6 +90,68 @@ class Signer:
                 ctypes.c_void_p(msg.data_ptr()), length, stride, m, ctypes.c_void_p(sig.data_ptr()), sig.stride(0),
                 _fault_ptr(fault), ctypes.c_void_p(stream))
         _lib.check(rc, "hsv_signer_sign_device")
+
+    def sign_transactions(self, txs, key_idx=None, offsets=None) -> np.ndarray:
+        """Mempool transactions ``message || pk || R || s`` (hsv_signer_sign_transactions):
+        a signed copy of ``txs``, whose last 96 bytes per transaction become pk
+        and the signature over SHA-512(message)[..32] -- what
+        ``mempool.verify_transactions`` accepts.  txs: (n, tx_size) uint8 of
+        equal transactions, or a flat buffer with ``offsets`` (n + 1 byte
+        offsets).  key_idx: (n,) key per item; None: item i uses key i; an
+        index >= nkeys gives 96 zero bytes.  A transaction shorter than 96
+        bytes raises."""
+        out = np.array(txs, dtype=np.uint8, order="C", copy=True)
+        idx = None if key_idx is None else np.ascontiguousarray(key_idx, np.uint32).reshape(-1)
+        if offsets is None:
+            if out.ndim != 2:
+                raise ValueError("expected an (n, tx_size) array, or a flat buffer and offsets")
+            n, size, offs = out.shape[0], out.shape[1], None
+        else:
+            offs = np.ascontiguousarray(offsets, np.uint64).reshape(-1)
+            out = out.reshape(-1)
+            n, size = offs.size - 1, 0
+            if n < 0 or (n and int(offs.max()) > out.size):
+                raise ValueError("offsets do not fit the buffer")
+        if idx is not None and idx.size != n:
+            raise ValueError("key_idx and txs differ in length")
+        if n > 0:
+            _lib.check(self._lib.hsv_signer_sign_transactions(
+                self._h, None if idx is None else _ptr(idx), ctypes.c_void_p(out.ctypes.data),
+                None if offs is None else _ptr(offs), size, n), "hsv_signer_sign_transactions")
+        return out
+
+    def sign_transactions_device(self, txs, offsets=None, tx_size=None, key_idx=None, stream=None, fault=None) -> None:
+        """In place on the device, enqueued on ``stream`` (default: torch's
+        current stream), no synchronisation.  txs: uint8 tensor at any byte
+        address; offsets: (n + 1,) int64 byte offsets relative to txs, or None
+        with ``tx_size`` (default: the row length of a 2-D txs) for equal
+        transactions; key_idx: (n,) int32 / uint32 or None; fault: optional
+        per-call fault words (verifier.verify_device).  A transaction shorter
+        than 96 bytes, or a decreasing pair of offsets, is left untouched."""
+        from .verifier import _fault_ptr
+        import torch
+        for t in (offsets, key_idx, fault):
+            if t is not None and t.device != txs.device:
+                raise ValueError(f"all tensors must live on {txs.device}, got {t.device}")
+        if offsets is not None:
+            n, size = offsets.numel() - 1, 0
+        else:
+            if tx_size is None:
+                if txs.dim() != 2 or not txs.is_contiguous():
+                    raise ValueError("tx_size is needed unless txs is a contiguous (n, tx_size) tensor")
+                tx_size = txs.shape[1]
+            size = int(tx_size)
+            n = txs.numel() // size if size else 0
+        if key_idx is not None and key_idx.numel() != n:
+            raise ValueError("key_idx and txs differ in length")
+        with torch.cuda.device(txs.device):
+            if stream is None:
+                stream = torch.cuda.current_stream(txs.device).cuda_stream
+            rc = self._lib.hsv_signer_sign_transactions_device(
+                self._h, ctypes.c_void_p(key_idx.data_ptr()) if key_idx is not None else None,
+                ctypes.c_void_p(txs.data_ptr()), ctypes.c_void_p(offsets.data_ptr()) if offsets is not None else None,
+                size, n, _fault_ptr(fault), ctypes.c_void_p(stream))
+        _lib.check(rc, "hsv_signer_sign_transactions_device")
 
     def close(self) -> None:
         if self._h:

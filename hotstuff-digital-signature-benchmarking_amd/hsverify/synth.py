@@ -221,3 +221,21 @@ def transactions(n: int, tx_size: int = 512, seed: int = 0, corrupt_frac: float 
             w.sig[i, 32] ^= np.uint8(1)
     txs = np.concatenate([msgs, w.pk, w.sig], axis=1)
     return TxWorkload(np.ascontiguousarray(txs), w.honest, w.kind, w.accept)
+
+
+def transactions_gpu(n: int, tx_size: int = 512, seed: int = 0) -> TxWorkload:
+    """The honest mempool workload of `transactions` (same seeds, same
+    messages: byte for byte `transactions(n, tx_size, seed, corrupt_frac=0.0)`),
+    hashed and signed on the GPU by `Signer.sign_transactions` instead of a
+    hashlib loop and host threads.  Every item is honest."""
+    from .signer import Signer
+    if tx_size < 96:
+        raise ValueError("a transaction carries pk and signature: tx_size >= 96")
+    mlen = tx_size - 96
+    rng = np.random.default_rng(seed)
+    seeds = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+    msgs = rng.integers(0, 256, size=(n, mlen), dtype=np.uint8)
+    txs = np.concatenate([msgs, np.zeros((n, 96), np.uint8)], axis=1)
+    with Signer(seeds) as s:
+        txs = s.sign_transactions(txs)
+    return TxWorkload(txs, np.ones(n, bool), np.full(n, -1, np.int8), np.ones(n, bool))

@@ -281,7 +281,8 @@ HSV_API int hsv_committee_verify_device(const hsv_committee *c, const uint32_t *
  * per-transaction flags are hsv_verify's flags for that (pk, sig, digest);
  * HSV_STRICT_OK is the reference's `signature.verify(..).is_ok()`.
  * Transactions shorter than 96 bytes (the reference's slice would panic) are
- * rejected with HSV_ERR_INVALID_ARG by the host-buffer calls. */
+ * rejected with HSV_ERR_INVALID_ARG by the host-buffer calls.  The signing
+ * mirror, for load generation, is hsv_signer_sign_transactions* below. */
 
 /* Ragged batch: transaction i is txs[offsets[i] .. offsets[i+1]) (n+1
  * offsets).  flags_out: n bytes. */
@@ -370,6 +371,43 @@ HSV_API int hsv_signer_sign(hsv_signer *s, const uint32_t *key_idx, const uint8_
 HSV_API int hsv_signer_sign_device(const hsv_signer *s, const uint32_t *d_key_idx, const uint8_t *d_msg, size_t msg_len,
                                    size_t msg_stride, size_t m, uint8_t *d_sig, size_t sig_stride, uint32_t *d_fault,
                                    void *stream);
+/* Sign mempool transactions in place: the signing mirror of
+ * hsv_verify_transactions*.  Fill in the last 96 bytes of every transaction:
+ * pk (32) || R || s (64), the signature over Digest(SHA-512(message)[..32])
+ * with message = the bytes before them -- what hsv_verify_transactions*
+ * accepts, bit-exact with hsv_public_key plus hsv_sign(seed,
+ * SHA-512(message)[..32], 32).  Message bytes are never written; the message
+ * may be empty (a 96-byte transaction).
+ * offsets != NULL: transaction i is txs[offsets[i] .. offsets[i+1]) (n+1
+ *                  entries, relative to txs).
+ * offsets == NULL: transaction i is txs[i*tx_size .. (i+1)*tx_size).
+ * txs, the offsets and tx_size may have any alignment.  key_idx == NULL: item
+ * i uses key i (n <= nkeys); otherwise key key_idx[i], and an index >= nkeys
+ * writes 96 zero bytes and raises no fault (as hsv_signer_sign writes a zero
+ * signature).  As the rest of the signer this path is NOT constant time: it is
+ * for load generation and input synthesis only, never for a key that matters.
+ * Host form: synchronous, on the signer's device; n == 0 does nothing.  A
+ * transaction shorter than 96 bytes, or decreasing offsets, return
+ * HSV_ERR_INVALID_ARG before anything is written (the length check of
+ * hsv_verify_transactions); a failed device self-check returns
+ * HSV_ERR_DEVICE_FAULT (that item: its pk and a zero signature).  There is no
+ * CPU fallback (HSV_ERR_NO_DEVICE without a GPU).  Plain staged copies on one
+ * device: this call is neither pipelined nor sharded across GPUs. */
+HSV_API int hsv_signer_sign_transactions(hsv_signer *s, const uint32_t *key_idx, uint8_t *txs,
+                                         const uint64_t *offsets, size_t tx_size, size_t n);
+/* Device-resident, stream-ordered form (device = the signer's: buffers or a
+ * stream of another device are HSV_ERR_INVALID_ARG); never synchronises.  A
+ * transaction shorter than 96 bytes, or one whose offsets decrease, is left
+ * completely untouched, and its neighbours are unaffected (with d_offsets NULL
+ * a tx_size below 96 is HSV_ERR_INVALID_ARG, as in
+ * hsv_verify_transactions_device).  d_fault (optional) as
+ * hsv_signer_sign_device: only d_fault[0] is ever set, by an item whose [r]B
+ * fails the self-check; that item gets its pk and a zero signature.  Batches
+ * above 2^22 items run as 2^22-item launches, in order on `stream`.  Every
+ * launch is two kernels: the message digests, then the signatures. */
+HSV_API int hsv_signer_sign_transactions_device(const hsv_signer *s, const uint32_t *d_key_idx, uint8_t *d_txs,
+                                                const uint64_t *d_offsets, size_t tx_size, size_t n,
+                                                uint32_t *d_fault, void *stream);
 
 /* Synthesis helper for the corrupted-input mixes (SURVEY 8(d) C3/C4 "mixed-
  * order A"; Appendix A.3 rows 7-8): the key A' = [a]B + [2*torsion+1]T8 (a

@@ -436,6 +436,27 @@ class Signer {
                                                d_fault, stream),
                         "hsv_signer_sign_device");
   }
+  // Mempool transactions message || pk || R || s, signed in place
+  // (hsv_signer_sign_transactions): n transactions at txs[offsets[i] ..
+  // offsets[i+1]) (n + 1 offsets), or of tx_size bytes each when offsets is
+  // nullptr; key key_idx[i] for item i (nullptr: key i).  The last 96 bytes of
+  // each become pk and the signature over SHA-512(message)[..32]; a
+  // transaction shorter than 96 bytes throws before anything is written.
+  void sign_transactions(const uint32_t *key_idx, uint8_t *txs, const uint64_t *offsets, size_t tx_size, size_t n) {
+    crypto::check_infra(hsv_signer_sign_transactions(h_, key_idx, txs, offsets, tx_size, n),
+                        "hsv_signer_sign_transactions");
+  }
+  // equal transactions of tx_size bytes, item i with key i
+  void sign_transactions(std::vector<uint8_t> &txs, size_t tx_size) {
+    sign_transactions(nullptr, txs.data(), nullptr, tx_size, tx_size ? txs.size() / tx_size : 0);
+  }
+  // device-resident, stream-ordered form (hsv_signer_sign_transactions_device)
+  void sign_transactions_device(const uint32_t *d_key_idx, uint8_t *d_txs, const uint64_t *d_offsets, size_t tx_size,
+                                size_t n, uint32_t *d_fault = nullptr, void *stream = nullptr) const {
+    crypto::check_infra(hsv_signer_sign_transactions_device(h_, d_key_idx, d_txs, d_offsets, tx_size, n, d_fault,
+                                                            stream),
+                        "hsv_signer_sign_transactions_device");
+  }
   hsv_signer *handle() const { return h_; }
 
  private:
