@@ -659,6 +659,25 @@ int call_fault_words(DevCtx &c, uint32_t *d_fault, hipStream_t stream, uint32_t 
   return HSV_OK;
 }
 
+int StagedBlock::alloc(const char *what, size_t zeroed) {
+  void *p = nullptr;
+  hipError_t e = hsv_ws_malloc(&p, size_ + kAlign, st_);
+  if (e != hipSuccess) return hip_fail(what, e);
+  d_ = static_cast<uint8_t *>(p);
+  e_ = hipMemsetAsync(d_, 0, zeroed ? kAlign + zeroed : kFaultBytes, st_);
+  return HSV_OK;
+}
+
+int StagedBlock::finish(const char *where) {
+  uint8_t words[kFaultBytes] = {0};
+  out(words, 0, kFaultBytes);
+  const hipError_t ef = hipFreeAsync(d_, st_);
+  const hipError_t es = hipStreamSynchronize(st_);  // nothing of this call stays in flight
+  step(ef);
+  step(es);
+  return ok() ? check_faults(words, where) : hip_fail(where, e_);
+}
+
 SideStreamLease::SideStreamLease(DevCtx &c) : c_(c) {
   std::lock_guard<std::mutex> lk(c.side_mu);
   if (!c.side_free.empty()) {
@@ -689,21 +708,41 @@ int pointer_device(const void *p) {
   return -1;
 }
 
-int device_for_call(const void *d_ptr, void *stream, int *dev) {
+int DeviceCall::begin(const void *d_ptr, void *stream_in, uint32_t *d_fault, Table table, const char *owner,
+                      int owner_device) {
+  int rc = ensure_init();
+  if (rc != HSV_OK) return rc;
   int d = pointer_device(d_ptr);
-  if (d < 0) {
-    if (hipGetDevice(&d) != hipSuccess) return fail(HSV_ERR_HIP, "hipGetDevice failed");
+  if (owner) {
+    if (d >= 0 && d != owner_device)
+      return fail(HSV_ERR_INVALID_ARG, "buffers live on device " + std::to_string(d) + ", the " + owner +
+                                           " on device " + std::to_string(owner_device));
+    d = owner_device;
+  } else {
+    if (d < 0 && hipGetDevice(&d) != hipSuccess) return fail(HSV_ERR_HIP, "hipGetDevice failed");
+    if (d < 0 || d >= device_count_inited())
+      return fail(HSV_ERR_INVALID_ARG, "device of the input pointers out of range");
   }
-  if (d < 0 || d >= device_count_inited()) return fail(HSV_ERR_INVALID_ARG, "device of the input pointers out of range");
+  stream = reinterpret_cast<hipStream_t>(stream_in);
   if (stream) {
     int sd = -1;
-    if (hipStreamGetDevice(reinterpret_cast<hipStream_t>(stream), &sd) == hipSuccess && sd >= 0 && sd != d)
-      return fail(HSV_ERR_INVALID_ARG, "inputs live on device " + std::to_string(d) + " but the stream belongs to device " +
-                                           std::to_string(sd));
+    if (hipStreamGetDevice(stream, &sd) == hipSuccess && sd >= 0 && sd != d)
+      return fail(HSV_ERR_INVALID_ARG, "the stream belongs to device " + std::to_string(sd) + ", the " +
+                                           (owner ? owner : "inputs") + " to device " + std::to_string(d));
     (void)hipGetLastError();
   }
-  *dev = d;
-  return HSV_OK;
+  guard_.emplace(d);
+  if (guard_->status() != hipSuccess) return hip_fail("hipSetDevice", guard_->status());
+  c = &ctx(d);
+  if (table == kVariant) {
+    v = variant();
+    rc = comb_table_for(*c, v, &comb);
+  } else {  // rebuilt here if hsv_shutdown released it
+    rc = table == kNarrow ? ensure_btable(*c) : ensure_btable16(*c);
+    comb = table == kNarrow ? c->d_btable : c->d_btable16;
+  }
+  if (rc != HSV_OK) return rc;
+  return call_fault_words(*c, d_fault, stream, &fault);
 }
 
 namespace {
@@ -1219,22 +1258,14 @@ int hsv_verify_device_bits(const uint8_t *d_pk, size_t pk_stride, const uint8_t 
   if (mis) return fail(HSV_ERR_ALIGN, "device pointers and strides must be multiples of 16");
   if (pk_stride < 32 || sig_stride < 64 || (msg_stride != 0 && msg_stride < 32))
     return fail(HSV_ERR_INVALID_ARG, "record strides overlap");
-  int rc = ensure_init();
+  DeviceCall call;
+  const int rc = call.begin(d_pk, stream, d_fault, DeviceCall::kVariant);
   if (rc != HSV_OK) return rc;
-  int dev = 0;
-  rc = device_for_call(d_pk, stream, &dev);
-  if (rc != HSV_OK) return rc;
-  DeviceGuard guard(dev);
-  if (guard.status() != hipSuccess) return hip_fail("hipSetDevice", guard.status());
-  const int v = variant();
-  const uint32_t *comb_b = nullptr;
-  DevCtx &c = ctx(dev);
-  rc = comb_table_for(c, v, &comb_b);
-  if (rc != HSV_OK) return rc;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  uint32_t *fault = nullptr;
-  rc = call_fault_words(c, d_fault, s, &fault);
-  if (rc != HSV_OK) return rc;
+  DevCtx &c = *call.c;
+  const int v = call.v;
+  const uint32_t *comb_b = call.comb;
+  uint32_t *fault = call.fault;
+  hipStream_t s = call.stream;
   // Batches of several kChunk launches alternate them over the caller's stream
   // and a second library stream leased for this call (fork/join through
   // events on the caller's stream): a chunk's launch starts on the SIMDs the

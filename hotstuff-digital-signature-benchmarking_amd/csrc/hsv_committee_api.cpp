@@ -693,24 +693,12 @@ int hsv_committee_verify_device(const hsv_committee *cm, const uint32_t *d_key_i
     return fail(HSV_ERR_ALIGN, "device pointers and strides must be multiples of 16");
   if (sig_stride < 64 || (msg_stride != 0 && msg_stride < 32)) return fail(HSV_ERR_INVALID_ARG, "record strides overlap");
   if (m > 0xffffffffu) return fail(HSV_ERR_INVALID_ARG, "batch too large");
-  int rc = ensure_init();
-  if (rc != HSV_OK) return rc;
-  const int pd = pointer_device(d_sig);
-  if (pd >= 0 && pd != cm->dev.device)
-    return fail(HSV_ERR_INVALID_ARG, "inputs live on device " + std::to_string(pd) + ", the committee on device " +
-                                         std::to_string(cm->dev.device));
-  DevCtx &c = ctx(cm->dev.device);
-  DeviceGuard guard(c.device);
-  if (guard.status() != hipSuccess) return hip_fail("hipSetDevice", guard.status());
-  rc = ensure_btable(c);  // the B table is rebuilt if hsv_shutdown released it
-  if (rc != HSV_OK) return rc;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  uint32_t *fault = nullptr;
-  rc = call_fault_words(c, d_fault, s, &fault);
+  DeviceCall call;
+  const int rc = call.begin(d_sig, stream, d_fault, DeviceCall::kNarrow, "committee", cm->dev.device);
   if (rc != HSV_OK) return rc;
   const hipError_t e = hsv_launch_comb_verify(d_key_idx, d_sig, sig_stride, d_msg, msg_stride, (uint32_t)m, cm->dev.d_pks,
-                                              cm->dev.d_kflags, cm->dev.n, cm->dev.d_tabptr, c.d_btable, d_flags, fault,
-                                              nullptr, s);
+                                              cm->dev.d_kflags, cm->dev.n, cm->dev.d_tabptr, call.comb, d_flags,
+                                              call.fault, nullptr, call.stream);
   return e == hipSuccess ? HSV_OK : hip_fail("committee verify launch", e);
 }
 

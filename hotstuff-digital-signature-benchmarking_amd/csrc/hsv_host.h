@@ -1,5 +1,14 @@
 // Host-side state shared by the C-ABI translation units (hsv_capi.cpp,
-// hsv_committee_api.cpp, hsv_tx.cpp).  Not part of the public ABI.
+// hsv_committee_api.cpp, hsv_tx.cpp, hsv_msgs_api.cpp, hsv_signer_api.cpp,
+// hsv_numa.cpp) and hsv_test_hooks.cpp.  Not part of the public ABI.
+//
+// The call layer every entry-point family is built from:
+//   * BatchSpan (hsv_batch.hpp): the chunk walk of a ragged or fixed-size host
+//     batch, a chunk's geometry and the length check;
+//   * StagedBlock: one pool block with aligned regions and the self-check
+//     words, drained by finish() -- the staged host forms;
+//   * DeviceCall: device, guard, B table and fault words of a stream-ordered
+//     device-form call.
 //
 // Device model (include/hsv.h, hsv_init):
 //   * one DevCtx per visible GPU, created lazily;
@@ -19,10 +28,12 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <vector>
 
 #include "hsv.h"
+#include "hsv_batch.hpp"
 #include "hsv_internal.h"
 
 #if defined(__SSE2__)
@@ -56,6 +67,10 @@ constexpr size_t kChunk = size_t(1) << 22;        // items per verification laun
 constexpr size_t kShardMin = size_t(1) << 16;     // shard host batches across devices at or above this
 constexpr size_t kZeroCopyMax = size_t(1) << 12;  // small batches read straight from pinned memory
 inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// Bytes of transactions or messages a host form stages per launch (one larger
+// item: alone).  Tests lower it through hsv_test_stage_bytes (libhsv_test.so).
+constexpr size_t kStageBytes = size_t(1) << 29;
+inline std::atomic<size_t> g_stage_bytes{kStageBytes};
 
 // Inputs a kernel reads straight from pinned memory (the zero-copy latency
 // form) are written with streaming stores, so they sit in DRAM and not in the
@@ -181,6 +196,45 @@ constexpr size_t kFaultOutWord = 4;  // d_fault[4..5]: output of hsv_launch_faul
 // `stream` here), or the per-device words when d_fault is NULL.
 int call_fault_words(DevCtx &c, uint32_t *d_fault, hipStream_t stream, uint32_t **out);
 
+// One stream-ordered block from the library pool for one launch of a staged
+// host form: the self-check words, then the regions add() lays out at kAlign
+// (and kAlign of slack after the last).  A step after a failed one is skipped;
+// finish() reports the first failure, and always frees the block and drains
+// the stream, so nothing of the call stays in flight.
+class StagedBlock {
+ public:
+  explicit StagedBlock(hipStream_t stream) : st_(stream) {}
+  size_t add(size_t bytes) {  // offset of a new region
+    const size_t off = size_;
+    size_ += round_up(bytes, kAlign);
+    return off;
+  }
+  // Allocates the block; zeroes the self-check words and the first `zeroed`
+  // bytes of the first region.  HSV_OK, or the error `what` names.
+  int alloc(const char *what, size_t zeroed = 0);
+  uint8_t *at(size_t off) const { return d_ + off; }
+  uint32_t *fault() const { return reinterpret_cast<uint32_t *>(d_); }
+  bool ok() const { return e_ == hipSuccess; }
+  void step(hipError_t e) {
+    if (ok()) e_ = e;
+  }
+  void in(size_t off, const void *src, size_t bytes) {
+    if (ok() && bytes) e_ = hipMemcpyAsync(d_ + off, src, bytes, hipMemcpyHostToDevice, st_);
+  }
+  void out(void *dst, size_t off, size_t bytes) {
+    if (ok() && bytes) e_ = hipMemcpyAsync(dst, d_ + off, bytes, hipMemcpyDeviceToHost, st_);
+  }
+  // Self-check words out, free, drain: HSV_OK, the first failed step's error,
+  // or HSV_ERR_DEVICE_FAULT (check_faults).
+  int finish(const char *where);
+
+ private:
+  hipStream_t st_;
+  uint8_t *d_ = nullptr;
+  size_t size_ = kAlign;  // the self-check words' region
+  hipError_t e_ = hipSuccess;
+};
+
 // A side stream of device c for one call (current device must be c.device),
 // returned to the pool when the lease ends: concurrent device-API calls never
 // share one, so a call's join event only waits for its own chunks.
@@ -231,10 +285,28 @@ int run_sharded(int k, const std::function<int(int shard, int device)> &fn);
 
 // Device owning a device pointer (hipPointerGetAttributes); -1 if unknown.
 int pointer_device(const void *p);
-// Resolve the device a device-API call runs on: the device of its input
-// pointers, checked against the stream's device.  Returns HSV_OK and sets
-// *dev, or an error.
-int device_for_call(const void *d_ptr, void *stream, int *dev);
+
+// What every stream-ordered device-form call does once its arguments have
+// passed their checks: ensure_init, the device it runs on, the stream's
+// device checked against it, that device made current for the object's
+// lifetime, the B table asked for, and the fault words (call_fault_words).
+// Pointer mode (owner == NULL): the device of d_ptr, else the current one.
+// Handle mode: owner_device, which d_ptr must not contradict (`owner` names
+// the handle in the error text).
+class DeviceCall {
+ public:
+  enum Table { kNarrow, kWide, kVariant };  // ensure_btable, ensure_btable16, comb_table_for(variant())
+  int begin(const void *d_ptr, void *stream, uint32_t *d_fault, Table table, const char *owner = nullptr,
+            int owner_device = -1);
+  DevCtx *c = nullptr;
+  hipStream_t stream = nullptr;
+  int v = 0;                       // variant() (kVariant only)
+  const uint32_t *comb = nullptr;  // the table asked for
+  uint32_t *fault = nullptr;
+
+ private:
+  std::optional<DeviceGuard> guard_;
+};
 
 // ---- hooks shared with hsv_test_hooks.cpp (exported by libhsv_test.so only) ----
 int auto_committee_corrupt_tables();  // zero the cached tables of the automatic committee
@@ -266,5 +338,8 @@ int resident_set_mode(int on);      // hsv_set_resident_service
 int run_host(const uint8_t *pk, size_t pk_stride, const uint8_t *sig, size_t sig_stride, const uint8_t *msg,
              size_t msg_stride, size_t n, uint8_t *flags_out);
 int batch_verdict(const uint8_t *flags, size_t n);
+// The length check of the transaction host forms (hsv_tx.cpp): HSV_OK, or
+// HSV_ERR_INVALID_ARG naming the first transaction shorter than 96 bytes.
+int tx_lengths_ok(const uint64_t *offsets, size_t tx_size, size_t n);
 
 }  // namespace hsvh

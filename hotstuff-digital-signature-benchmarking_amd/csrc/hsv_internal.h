@@ -81,6 +81,36 @@ double hsv_launch_mad_peak(int device_cus);
 }
 #endif
 
+#ifdef __cplusplus
+namespace hsv {
+// A launcher's workspace: the caller's when it holds `need` bytes (a pipeline
+// that keeps one per stream), else a block from the library pool, which
+// done() frees on the stream.
+class Workspace {
+ public:
+  Workspace(void *ws_in, size_t ws_cap, size_t need, hipStream_t stream) : stream_(stream) {
+    if (ws_in && ws_cap >= need)
+      p_ = ws_in;
+    else
+      e_ = hsv_ws_malloc(&own_, need, stream);
+  }
+  hipError_t status() const { return e_; }
+  uint8_t *get() const { return static_cast<uint8_t *>(own_ ? own_ : p_); }
+  // the launcher's result: e, or the free's status when e is hipSuccess
+  hipError_t done(hipError_t e) {
+    const hipError_t ef = own_ ? hipFreeAsync(own_, stream_) : hipSuccess;
+    own_ = nullptr;
+    return e != hipSuccess ? e : ef;
+  }
+
+ private:
+  hipStream_t stream_;
+  void *p_ = nullptr, *own_ = nullptr;
+  hipError_t e_ = hipSuccess;
+};
+}  // namespace hsv
+#endif
+
 // ---- committee key cache (hsv_committee.hip) -----------------------------
 // Request block of the resident committee service (hsv_comb_resident_kernel,
 // csrc/hsv_committee.hip), in coherent pinned host memory.  The request's

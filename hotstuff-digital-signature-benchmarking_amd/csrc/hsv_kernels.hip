@@ -982,7 +982,6 @@ uint32_t next_nonce() {
 }
 
 
-
 // Two-pass launch (variants 19/20): prepass over all items, then the
 // persistent point pass.  Workspace: per-lane tables | counters (256 B) |
 // fallback list (4 B per item) | prep records (kPrepWords x 4 B per item).
@@ -1057,14 +1056,10 @@ hipError_t launch_hp(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, 
     *ws_need = need;
     return hipSuccess;
   }
-  // the caller's workspace when it is large enough (a pipeline that keeps one
-  // per stream), else one from the library pool, freed on the stream
-  void *ws = ws_in && ws_cap >= need ? ws_in : nullptr;
-  const bool own = ws == nullptr;
-  if (own) e = hsv_ws_malloc(&ws, need, stream);
-  if (e != hipSuccess) return e;
-  uint8_t *ws8 = static_cast<uint8_t *>(ws);
-  uint4 *vt_ws = reinterpret_cast<uint4 *>(ws);
+  hsv::Workspace ws(ws_in, ws_cap, need, stream);
+  if (ws.status() != hipSuccess) return ws.status();
+  uint8_t *ws8 = ws.get();
+  uint4 *vt_ws = reinterpret_cast<uint4 *>(ws8);
   hsv::HcCounters *ctr = reinterpret_cast<hsv::HcCounters *>(ws8 + ws_bytes);
   uint32_t *canary = reinterpret_cast<uint32_t *>(ws8 + ws_bytes + 256);
   uint32_t *fb_list = reinterpret_cast<uint32_t *>(ws8 + ws_bytes + 256 + canary_bytes);
@@ -1078,8 +1073,7 @@ hipError_t launch_hp(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, 
       e = hsv_launch_tx_fused(grid, tx->txs, tx->offsets, tx->tx_size, n, tx->records, rec, ctr, fb_list, ready,
                               g_lat_bits.load(), flags_out, strict_bits, vt_ws, comb_b, canary, next_nonce(), t_inject,
                               fault, stream);
-    const hipError_t ef = own ? hipFreeAsync(ws, stream) : hipSuccess;
-    return e != hipSuccess ? e : ef;
+    return ws.done(e);
   }
   if (e == hipSuccess && tx) {
     static_assert(WA == 4, "hsv_launch_tx_prep writes the WA = 4 prepass record");
@@ -1110,8 +1104,7 @@ hipError_t launch_hp(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, 
     }
     e = hipGetLastError();
   }
-  const hipError_t ef = own ? hipFreeAsync(ws, stream) : hipSuccess;
-  return e != hipSuccess ? e : ef;
+  return ws.done(e);
 }
 
 // Latency form (variant 21 below kPairMax items): one launch of the fused
@@ -1127,36 +1120,6 @@ constexpr uint32_t kPairMax = 1u << 13;
 // 0.477 at 3072, 0.626 / 0.487 at 4096.
 constexpr uint32_t kRowMaxDefault = 3072;
 
-template <int WA, int CB>
-hipError_t launch_pair(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, uint64_t sig_stride,
-                       const uint8_t *msg, uint64_t msg_stride, uint32_t n, uint8_t *flags_out,
-                       uint32_t *strict_bits, const uint32_t *comb_b, uint32_t *fault, hipStream_t stream,
-                       void *ws_in = nullptr, size_t ws_cap = 0, size_t *ws_need = nullptr) {
-  const uint32_t grid = (n + hsv::kFusedItems - 1) / hsv::kFusedItems;
-  const size_t slots = (size_t)grid * 2u * hsv::kFusedItems;
-  const size_t ws_bytes = slots * hsv::vt_lane_uint4<WA>() * sizeof(uint4);
-  const size_t need = ws_bytes + slots * sizeof(uint32_t);
-  if (ws_need) {
-    *ws_need = need;
-    return hipSuccess;
-  }
-  void *ws = ws_in && ws_cap >= need ? ws_in : nullptr;
-  const bool own = ws == nullptr;
-  hipError_t e = own ? hsv_ws_malloc(&ws, need, stream) : hipSuccess;
-  if (e != hipSuccess) return e;
-  if (strict_bits) e = hipMemsetAsync(strict_bits, 0, (size_t)((n + 31u) / 32u) * 4u, stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL((hsv::hsv_verify_pair_fused_kernel<WA, CB>), dim3(grid), dim3(3 * 64), 0, stream, pk,
-                       pk_stride, sig, sig_stride, msg, msg_stride, n, flags_out, strict_bits,
-                       static_cast<uint4 *>(ws), comb_b, g_lat_bits.load(),
-                       reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(ws) + ws_bytes), next_nonce(),
-                       t_inject, fault);
-    e = hipGetLastError();
-  }
-  const hipError_t ef = own ? hipFreeAsync(ws, stream) : hipSuccess;
-  return e != hipSuccess ? e : ef;
-}
-
 // Row form (variant 21 above kJointMax, at <= row_max() items): kRowItemsOf<1>
 // items per block of four waves.  The workspace holds one full-length table
 // and one canary per row (the fallback path's tables; the row tables live in
@@ -1166,99 +1129,62 @@ hipError_t launch_pair(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig
 // only RR = 1 is instantiated.
 constexpr uint32_t row_max() { return kRowMaxDefault; }
 
+// The small form n <= kPairMax items of variant 21 take: its kernel (all four
+// have one signature), grid, block size and workspace slots -- one
+// full-length table and one canary per slot.
+//   quad  (<= kQuadMax): one item per block of three waves, a slot per point wave;
+//   joint (<= kJointMax): kJointItems items per block, a slot per point wave;
+//   row   (<= row_max()): see above, a slot per row;
+//   pair  (<= kPairMax): see above, a slot per pair lane.
 template <int WA, int CB>
-hipError_t launch_row(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, uint64_t sig_stride,
-                      const uint8_t *msg, uint64_t msg_stride, uint32_t n, uint8_t *flags_out,
-                      uint32_t *strict_bits, const uint32_t *comb_b, uint32_t *fault, hipStream_t stream,
-                      void *ws_in = nullptr, size_t ws_cap = 0, size_t *ws_need = nullptr) {
-  const uint32_t items = hsv::kRowItemsOf<1>;
-  const uint32_t grid = (n + items - 1) / items;
-  const size_t slots = (size_t)grid * hsv::kRowRows;
-  const size_t ws_bytes = slots * hsv::vt_lane_uint4<WA>() * sizeof(uint4);
-  const size_t need = ws_bytes + slots * sizeof(uint32_t);
-  if (ws_need) {
-    *ws_need = need;
-    return hipSuccess;
+struct SmallForm {
+  decltype(&hsv::hsv_verify_quad_kernel<WA, CB>) kern;
+  uint32_t grid, block;
+  size_t slots;
+  explicit SmallForm(uint32_t n) {
+    if (n <= hsv::kQuadMax) {
+      kern = hsv::hsv_verify_quad_kernel<WA, CB>;
+      grid = n, block = 4 * 64, slots = (size_t)grid * 2u;
+    } else if (n <= hsv::kJointMax) {
+      kern = hsv::hsv_verify_joint_kernel<WA, CB>;
+      grid = (n + hsv::kJointItems - 1) / hsv::kJointItems, block = (hsv::kJointItems + 1) * 64;
+      slots = (size_t)grid * hsv::kJointItems;
+    } else if (n <= row_max()) {
+      kern = hsv::hsv_verify_row_kernel<WA, CB, 1>;
+      grid = (n + hsv::kRowItemsOf<1> - 1) / hsv::kRowItemsOf<1>, block = 4 * 64;
+      slots = (size_t)grid * hsv::kRowRows;
+    } else {
+      kern = hsv::hsv_verify_pair_fused_kernel<WA, CB>;
+      grid = (n + hsv::kFusedItems - 1) / hsv::kFusedItems, block = 3 * 64;
+      slots = (size_t)grid * 2u * hsv::kFusedItems;
+    }
   }
-  void *ws = ws_in && ws_cap >= need ? ws_in : nullptr;
-  const bool own = ws == nullptr;
-  hipError_t e = own ? hsv_ws_malloc(&ws, need, stream) : hipSuccess;
-  if (e != hipSuccess) return e;
-  if (strict_bits) e = hipMemsetAsync(strict_bits, 0, (size_t)((n + 31u) / 32u) * 4u, stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL((hsv::hsv_verify_row_kernel<WA, CB, 1>), dim3(grid), dim3(4 * 64), 0, stream, pk, pk_stride, sig, sig_stride, msg, msg_stride,
-                       n, flags_out, strict_bits, static_cast<uint4 *>(ws), comb_b, g_lat_bits.load(),
-                       reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(ws) + ws_bytes), next_nonce(),
-                       t_inject, fault);
-    e = hipGetLastError();
-  }
-  const hipError_t ef = own ? hipFreeAsync(ws, stream) : hipSuccess;
-  return e != hipSuccess ? e : ef;
-}
+};
 
-// Quad form (variant 21 at <= kQuadMax items): one item per block of three
-// waves.  The workspace holds one full-length table and one canary per point
-// wave (the fallback path's tables; the quad tables live in LDS).
 template <int WA, int CB>
-hipError_t launch_quad(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, uint64_t sig_stride,
-                       const uint8_t *msg, uint64_t msg_stride, uint32_t n, uint8_t *flags_out,
-                       uint32_t *strict_bits, const uint32_t *comb_b, uint32_t *fault, hipStream_t stream,
-                       void *ws_in = nullptr, size_t ws_cap = 0, size_t *ws_need = nullptr) {
-  const uint32_t grid = n;
-  const size_t slots = (size_t)grid * 2u;
-  const size_t ws_bytes = slots * hsv::vt_lane_uint4<WA>() * sizeof(uint4);
-  const size_t need = ws_bytes + slots * sizeof(uint32_t);
-  if (ws_need) {
-    *ws_need = need;
-    return hipSuccess;
-  }
-  void *ws = ws_in && ws_cap >= need ? ws_in : nullptr;
-  const bool own = ws == nullptr;
-  hipError_t e = own ? hsv_ws_malloc(&ws, need, stream) : hipSuccess;
-  if (e != hipSuccess) return e;
-  if (strict_bits) e = hipMemsetAsync(strict_bits, 0, (size_t)((n + 31u) / 32u) * 4u, stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL((hsv::hsv_verify_quad_kernel<WA, CB>), dim3(grid), dim3(4 * 64), 0, stream, pk, pk_stride,
-                       sig, sig_stride, msg, msg_stride, n, flags_out, strict_bits, static_cast<uint4 *>(ws), comb_b,
-                       g_lat_bits.load(), reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(ws) + ws_bytes),
-                       next_nonce(), t_inject, fault);
-    e = hipGetLastError();
-  }
-  const hipError_t ef = own ? hipFreeAsync(ws, stream) : hipSuccess;
-  return e != hipSuccess ? e : ef;
-}
-
-// Joint quad form (variant 21 above kQuadMax, at <= kJointMax items):
-// kJointItems items per block; one full-length table and one canary per
-// point wave in the workspace.
-template <int WA, int CB>
-hipError_t launch_joint(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, uint64_t sig_stride,
+hipError_t launch_small(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, uint64_t sig_stride,
                         const uint8_t *msg, uint64_t msg_stride, uint32_t n, uint8_t *flags_out,
                         uint32_t *strict_bits, const uint32_t *comb_b, uint32_t *fault, hipStream_t stream,
                         void *ws_in = nullptr, size_t ws_cap = 0, size_t *ws_need = nullptr) {
-  const uint32_t grid = (n + hsv::kJointItems - 1) / hsv::kJointItems;
-  const size_t slots = (size_t)grid * hsv::kJointItems;
-  const size_t ws_bytes = slots * hsv::vt_lane_uint4<WA>() * sizeof(uint4);
-  const size_t need = ws_bytes + slots * sizeof(uint32_t);
-  if (ws_need) {
+  const SmallForm<WA, CB> f(n);
+  const size_t ws_bytes = f.slots * hsv::vt_lane_uint4<WA>() * sizeof(uint4);
+  const size_t need = ws_bytes + f.slots * sizeof(uint32_t);
+  if (ws_need) {  // size query only
     *ws_need = need;
     return hipSuccess;
   }
-  void *ws = ws_in && ws_cap >= need ? ws_in : nullptr;
-  const bool own = ws == nullptr;
-  hipError_t e = own ? hsv_ws_malloc(&ws, need, stream) : hipSuccess;
+  hsv::Workspace ws(ws_in, ws_cap, need, stream);
+  hipError_t e = ws.status();
   if (e != hipSuccess) return e;
   if (strict_bits) e = hipMemsetAsync(strict_bits, 0, (size_t)((n + 31u) / 32u) * 4u, stream);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL((hsv::hsv_verify_joint_kernel<WA, CB>), dim3(grid), dim3((hsv::kJointItems + 1) * 64), 0,
-                       stream, pk, pk_stride, sig, sig_stride, msg, msg_stride, n, flags_out, strict_bits,
-                       static_cast<uint4 *>(ws), comb_b, g_lat_bits.load(),
-                       reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(ws) + ws_bytes), next_nonce(), t_inject,
+    hipLaunchKernelGGL(f.kern, dim3(f.grid), dim3(f.block), 0, stream, pk, pk_stride, sig, sig_stride, msg,
+                       msg_stride, n, flags_out, strict_bits, reinterpret_cast<uint4 *>(ws.get()), comb_b,
+                       g_lat_bits.load(), reinterpret_cast<uint32_t *>(ws.get() + ws_bytes), next_nonce(), t_inject,
                        fault);
     e = hipGetLastError();
   }
-  const hipError_t ef = own ? hipFreeAsync(ws, stream) : hipSuccess;
-  return e != hipSuccess ? e : ef;
+  return ws.done(e);
 }
 
 }  // namespace
@@ -1272,36 +1198,18 @@ extern "C" hipError_t hsv_launch_verify_ws(int variant, const uint8_t *pk, uint6
     return hsv_launch_verify(variant, pk, pk_stride, sig, sig_stride, msg, msg_stride, n, flags_out, strict_bits,
                              comb_b, fault, stream);
   if (!comb_b || !fault) return hipErrorInvalidValue;
-  if (variant == 21 && n <= hsv::kQuadMax)
-    return launch_quad<4, 16>(pk, pk_stride, sig, sig_stride, msg, msg_stride, n, flags_out, strict_bits, comb_b,
-                              fault, stream, ws, ws_cap);
-  if (variant == 21 && n <= hsv::kJointMax)
-    return launch_joint<4, 16>(pk, pk_stride, sig, sig_stride, msg, msg_stride, n, flags_out, strict_bits, comb_b,
-                               fault, stream, ws, ws_cap);
-  if (variant == 21 && n <= row_max())
-    return launch_row<4, 16>(pk, pk_stride, sig, sig_stride, msg, msg_stride, n, flags_out, strict_bits, comb_b,
-                             fault, stream, ws, ws_cap);
   if (variant == 21 && n <= kPairMax)
-    return launch_pair<4, 16>(pk, pk_stride, sig, sig_stride, msg, msg_stride, n, flags_out, strict_bits, comb_b,
-                              fault, stream, ws, ws_cap);
+    return launch_small<4, 16>(pk, pk_stride, sig, sig_stride, msg, msg_stride, n, flags_out, strict_bits, comb_b,
+                               fault, stream, ws, ws_cap);
   return launch_hp<4, HSV_HP_WAVES, 16>(pk, pk_stride, sig, sig_stride, msg, msg_stride, n, flags_out, strict_bits,
                                         comb_b, fault, stream, nullptr, ws, ws_cap);
 }
 
 extern "C" size_t hsv_launch_ws_bytes(int variant, uint32_t n) {
   size_t need = 0;
-  if (variant == 21 && n <= hsv::kQuadMax)
-    (void)launch_quad<4, 16>(nullptr, 0, nullptr, 0, nullptr, 0, n, nullptr, nullptr, nullptr, nullptr, nullptr,
-                             nullptr, 0, &need);
-  else if (variant == 21 && n <= hsv::kJointMax)
-    (void)launch_joint<4, 16>(nullptr, 0, nullptr, 0, nullptr, 0, n, nullptr, nullptr, nullptr, nullptr, nullptr,
+  if (variant == 21 && n <= kPairMax)
+    (void)launch_small<4, 16>(nullptr, 0, nullptr, 0, nullptr, 0, n, nullptr, nullptr, nullptr, nullptr, nullptr,
                               nullptr, 0, &need);
-  else if (variant == 21 && n <= row_max())
-    (void)launch_row<4, 16>(nullptr, 0, nullptr, 0, nullptr, 0, n, nullptr, nullptr, nullptr, nullptr, nullptr,
-                            nullptr, 0, &need);
-  else if (variant == 21 && n <= kPairMax)
-    (void)launch_pair<4, 16>(nullptr, 0, nullptr, 0, nullptr, 0, n, nullptr, nullptr, nullptr, nullptr, nullptr,
-                             nullptr, 0, &need);
   else if (variant == 19 || variant == 21)
     (void)launch_hp<4, HSV_HP_WAVES, 16>(nullptr, 0, nullptr, 0, nullptr, 0, n, nullptr, nullptr, nullptr, nullptr,
                                          nullptr, nullptr, nullptr, 0, &need);
@@ -1321,18 +1229,9 @@ extern "C" hipError_t hsv_launch_verify(int variant, const uint8_t *pk, uint64_t
       return launch_hp<4, 3, 16>(pk, pk_stride, sig, sig_stride, msg, msg_stride, n, flags_out, strict_bits, comb_b,
                                  fault, stream);
     case 21:
-      if (n <= hsv::kQuadMax)
-        return launch_quad<4, 16>(pk, pk_stride, sig, sig_stride, msg, msg_stride, n, flags_out, strict_bits, comb_b,
-                                  fault, stream);
-      if (n <= hsv::kJointMax)
-        return launch_joint<4, 16>(pk, pk_stride, sig, sig_stride, msg, msg_stride, n, flags_out, strict_bits, comb_b,
-                                   fault, stream);
-      if (n <= row_max())
-        return launch_row<4, 16>(pk, pk_stride, sig, sig_stride, msg, msg_stride, n, flags_out, strict_bits, comb_b,
-                                 fault, stream);
       if (n <= kPairMax)
-        return launch_pair<4, 16>(pk, pk_stride, sig, sig_stride, msg, msg_stride, n, flags_out, strict_bits, comb_b,
-                                  fault, stream);
+        return launch_small<4, 16>(pk, pk_stride, sig, sig_stride, msg, msg_stride, n, flags_out, strict_bits, comb_b,
+                                   fault, stream);
       return launch_hp<4, HSV_HP_WAVES, 16>(pk, pk_stride, sig, sig_stride, msg, msg_stride, n, flags_out, strict_bits,
                                             comb_b, fault, stream);
     default: return hipErrorInvalidValue;

@@ -14,8 +14,6 @@ using namespace hsvh;
 
 namespace {
 
-constexpr size_t kMsgChunkBytes = size_t(1) << 29;  // message bytes staged per launch (one longer message: alone)
-
 // launches of at most kChunk items, one after the other on `stream`
 hipError_t msgs_chunks(const uint8_t *d_pk, size_t pk_stride, const uint8_t *d_sig, size_t sig_stride,
                        const uint8_t *d_msgs, const uint64_t *d_offsets, size_t msg_len, size_t msg_stride, size_t n,
@@ -31,16 +29,6 @@ hipError_t msgs_chunks(const uint8_t *d_pk, size_t pk_stride, const uint8_t *d_s
                                d_bits ? d_bits + base / 32 : nullptr, comb16, fault, stream);
   }
   return e;
-}
-
-// bytes of the caller's buffer that items [a, b) span, from byte *first
-size_t span_bytes(const uint64_t *offsets, size_t msg_len, size_t msg_stride, size_t a, size_t b, size_t *first) {
-  if (offsets) {
-    *first = (size_t)offsets[a];
-    return (size_t)(offsets[b] - offsets[a]);
-  }
-  *first = a * msg_stride;
-  return msg_stride ? (b - a - 1) * msg_stride + msg_len : msg_len;
 }
 
 }  // namespace
@@ -60,22 +48,11 @@ int hsv_verify_msgs_device(const uint8_t *d_pk, size_t pk_stride, const uint8_t 
   if (reinterpret_cast<uintptr_t>(d_offsets) & 7u) return fail(HSV_ERR_ALIGN, "d_offsets must be 8-byte aligned");
   if (pk_stride < 32 || sig_stride < 64) return fail(HSV_ERR_INVALID_ARG, "record strides overlap");
   if (!d_offsets && msg_stride != 0 && msg_stride < msg_len) return fail(HSV_ERR_INVALID_ARG, "messages overlap");
-  int rc = ensure_init();
-  if (rc != HSV_OK) return rc;
-  int dev = 0;
-  rc = device_for_call(d_pk, stream, &dev);
-  if (rc != HSV_OK) return rc;
-  DeviceGuard guard(dev);
-  if (guard.status() != hipSuccess) return hip_fail("hipSetDevice", guard.status());
-  DevCtx &c = ctx(dev);
-  rc = ensure_btable16(c);
-  if (rc != HSV_OK) return rc;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  uint32_t *fault = nullptr;
-  rc = call_fault_words(c, d_fault, s, &fault);
+  DeviceCall call;
+  const int rc = call.begin(d_pk, stream, d_fault, DeviceCall::kWide);
   if (rc != HSV_OK) return rc;
   const hipError_t e = msgs_chunks(d_pk, pk_stride, d_sig, sig_stride, d_msgs, d_offsets, msg_len, msg_stride, n,
-                                   d_flags, d_strict_bits, c.d_btable16, fault, s);
+                                   d_flags, d_strict_bits, call.comb, call.fault, call.stream);
   return e == hipSuccess ? HSV_OK : hip_fail("message verify launch", e);
 }
 
@@ -85,13 +62,11 @@ int hsv_verify_msgs(const uint8_t *pk, const uint8_t *sig, const uint8_t *msgs, 
   if (n == 0) return HSV_OK;
   if (!pk || !sig || !flags_out) return fail(HSV_ERR_INVALID_ARG, "null pointer");
   if (n > 0xffffffffu) return fail(HSV_ERR_INVALID_ARG, "batch too large");
-  bool any_bytes = !offsets && msg_len != 0;
+  bool any_bytes = msg_len != 0;
   if (offsets) {
-    for (size_t i = 0; i < n; ++i) {
-      if (offsets[i + 1] < offsets[i])
-        return fail(HSV_ERR_INVALID_ARG, "offsets decrease at message " + std::to_string(i));
-      any_bytes |= offsets[i + 1] != offsets[i];
-    }
+    const size_t bad = first_bad_item(offsets, n, 0);
+    if (bad != n) return fail(HSV_ERR_INVALID_ARG, "offsets decrease at message " + std::to_string(bad));
+    any_bytes = offsets[n] != offsets[0];
   } else if (msg_stride != 0 && msg_stride < msg_len) {
     return fail(HSV_ERR_INVALID_ARG, "messages overlap");
   }
@@ -108,53 +83,33 @@ int hsv_verify_msgs(const uint8_t *pk, const uint8_t *sig, const uint8_t *msgs, 
   rc = slot_prepare(slot, 0, 0);
   if (rc != HSV_OK) return rc;
   hipStream_t st = slot.stream;
+  const BatchSpan span{offsets, msg_stride, msg_len};
   std::vector<uint64_t> rel;  // a chunk's offsets, relative to its first byte
-  for (size_t a = 0; a < n;) {
-    // items [a, b): at most kChunk, and at most kMsgChunkBytes of messages unless one message is longer
-    size_t b = a + 1, first = 0;
-    if (!offsets) {
-      const size_t per = msg_stride ? std::max<size_t>(1, kMsgChunkBytes / msg_stride) : kChunk;
-      b = std::min(n, a + std::min(kChunk, per));
-    } else {
-      while (b < n && b - a < kChunk && offsets[b + 1] - offsets[a] <= kMsgChunkBytes) ++b;
-    }
-    const size_t m = b - a;
-    const size_t bytes = span_bytes(offsets, msg_len, msg_stride, a, b, &first);
-    // one stream-ordered block from the library pool:
-    // pk | sig | flags | fault words | offsets | message bytes
-    const size_t off_sig = round_up(m * 32, kAlign), off_flags = off_sig + round_up(m * 64, kAlign);
-    const size_t off_fault = off_flags + round_up(m, kAlign), off_offs = off_fault + kAlign;
-    const size_t off_msg = off_offs + round_up(offsets ? (m + 1) * 8 : 0, kAlign);
-    void *blk = nullptr;
-    hipError_t e = hsv_ws_malloc(&blk, off_msg + bytes + kAlign, st);
-    if (e != hipSuccess) return hip_fail("allocating the message verification buffers", e);
-    uint8_t *d = static_cast<uint8_t *>(blk);
-    uint32_t *d_fault = reinterpret_cast<uint32_t *>(d + off_fault);
-    uint64_t *d_offs = offsets ? reinterpret_cast<uint64_t *>(d + off_offs) : nullptr;
-    uint8_t words[kFaultBytes] = {0};
-    // unwritten flags read as rejections; self-check words start at zero
-    e = hipMemsetAsync(d + off_flags, 0, off_fault + kFaultBytes - off_flags, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d, pk + a * 32, m * 32, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d + off_sig, sig + a * 64, m * 64, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && offsets) {
-      rel.resize(m + 1);
-      for (size_t k = 0; k <= m; ++k) rel[k] = offsets[a + k] - offsets[a];
-      e = hipMemcpyAsync(d_offs, rel.data(), (m + 1) * 8, hipMemcpyHostToDevice, st);
-    }
-    if (e == hipSuccess && bytes) e = hipMemcpyAsync(d + off_msg, msgs + first, bytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess)
-      e = hsv_launch_verify_msgs(d, 32, d + off_sig, 64, d + off_msg, d_offs, msg_len, msg_stride, (uint32_t)m,
-                                 d + off_flags, nullptr, c.d_btable16, d_fault, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(flags_out + a, d + off_flags, m, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(words, d_fault, kFaultBytes, hipMemcpyDeviceToHost, st);
-    const hipError_t ef = hipFreeAsync(blk, st);
-    const hipError_t es = hipStreamSynchronize(st);  // nothing of this call stays in flight
-    if (e == hipSuccess) e = ef;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return hip_fail("hsv_verify_msgs", e);
-    rc = check_faults(words, "hsv_verify_msgs");
+  for (size_t a = 0, b; a < n; a = b) {
+    b = span.chunk_end(a, n, kChunk, g_stage_bytes.load());
+    const size_t m = b - a, bytes = span.span_bytes(a, b);
+    StagedBlock blk(st);
+    const size_t off_flags = blk.add(m), off_pk = blk.add(m * 32), off_sig = blk.add(m * 64);
+    const size_t off_offs = blk.add(offsets ? (m + 1) * 8 : 0), off_msg = blk.add(bytes);
+    // unwritten flags read as rejections
+    rc = blk.alloc("allocating the message verification buffers", m);
     if (rc != HSV_OK) return rc;
-    a = b;
+    blk.in(off_pk, pk + a * 32, m * 32);
+    blk.in(off_sig, sig + a * 64, m * 64);
+    if (offsets) {
+      rel.resize(m + 1);
+      span.rel_offsets(a, b, rel.data());
+      blk.in(off_offs, rel.data(), (m + 1) * 8);
+    }
+    blk.in(off_msg, msgs + span.first_byte(a), bytes);
+    if (blk.ok())
+      blk.step(hsv_launch_verify_msgs(blk.at(off_pk), 32, blk.at(off_sig), 64, blk.at(off_msg),
+                                      offsets ? reinterpret_cast<uint64_t *>(blk.at(off_offs)) : nullptr, msg_len,
+                                      msg_stride, (uint32_t)m, blk.at(off_flags), nullptr, c.d_btable16, blk.fault(),
+                                      st));
+    blk.out(flags_out + a, off_flags, m);
+    rc = blk.finish("hsv_verify_msgs");
+    if (rc != HSV_OK) return rc;
   }
   return HSV_OK;
 }

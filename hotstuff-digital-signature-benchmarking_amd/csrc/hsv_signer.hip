@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "hsv_internal.h"
 #include "hsv_sign_core.hpp"
@@ -87,23 +88,16 @@ Grid grid_for(uint64_t n, int group) {
   return {(uint32_t)blocks, (size_t)(blocks * per_block * hsv::kSignWsWords * sizeof(uint32_t))};
 }
 
-template <int G>
-void launch_keygen(const hsv::KeygenArgs &a, uint32_t blocks, uint32_t *ws, uint32_t *fault, hipStream_t stream) {
-  hipLaunchKernelGGL((hsv::hsv_keygen_kernel<G>), dim3(blocks), dim3(hsv::kSignBlock), 0, stream, a, ws, fault);
-}
-
-template <int G>
-void launch_sign(const hsv::SignArgs &a, uint32_t blocks, uint32_t *ws, uint32_t *fault, hipStream_t stream) {
-  if (a.msg_len == 32)
-    hipLaunchKernelGGL((hsv::hsv_sign_kernel<G, true>), dim3(blocks), dim3(hsv::kSignBlock), 0, stream, a, ws, fault);
-  else
-    hipLaunchKernelGGL((hsv::hsv_sign_kernel<G, false>), dim3(blocks), dim3(hsv::kSignBlock), 0, stream, a, ws, fault);
-}
-
-template <int G>
-void launch_tx_sign(const hsv::SignArgs &a, const hsv::TxSignIo &io, uint32_t blocks, uint32_t *ws, uint32_t *fault,
-                    hipStream_t stream) {
-  hipLaunchKernelGGL((hsv::hsv_tx_sign_kernel<G>), dim3(blocks), dim3(hsv::kSignBlock), 0, stream, a, io, ws, fault);
+// fn(std::integral_constant<int, G>) for the built G that `group` names
+template <class Fn>
+void with_group(int group, Fn &&fn) {
+  switch (group) {
+    case 1: fn(std::integral_constant<int, 1>{}); break;
+    case 2: fn(std::integral_constant<int, 2>{}); break;
+    case 4: fn(std::integral_constant<int, 4>{}); break;
+    case 8: fn(std::integral_constant<int, 8>{}); break;
+    default: fn(std::integral_constant<int, 16>{}); break;
+  }
 }
 
 }  // namespace
@@ -124,21 +118,15 @@ extern "C" hipError_t hsv_launch_keygen(const uint8_t *seeds, uint32_t n, uint8_
   if (n > (1u << 22)) return hipErrorInvalidValue;
   const int group = g_group.load();
   const Grid gr = grid_for(n, group);
-  void *ws = nullptr;
-  hipError_t e = hsv_ws_malloc(&ws, gr.ws_bytes, stream);
-  if (e != hipSuccess) return e;
+  hsv::Workspace ws(nullptr, 0, gr.ws_bytes, stream);
+  if (ws.status() != hipSuccess) return ws.status();
   const hsv::KeygenArgs a{seeds, n, keys, comb16, hsv::kInjectNone, 0u};
-  uint32_t *w = static_cast<uint32_t *>(ws);
-  switch (group) {
-    case 1: launch_keygen<1>(a, gr.blocks, w, fault, stream); break;
-    case 2: launch_keygen<2>(a, gr.blocks, w, fault, stream); break;
-    case 4: launch_keygen<4>(a, gr.blocks, w, fault, stream); break;
-    case 8: launch_keygen<8>(a, gr.blocks, w, fault, stream); break;
-    default: launch_keygen<16>(a, gr.blocks, w, fault, stream); break;
-  }
-  e = hipGetLastError();
-  const hipError_t ef = hipFreeAsync(ws, stream);
-  return e != hipSuccess ? e : ef;
+  uint32_t *w = reinterpret_cast<uint32_t *>(ws.get());
+  with_group(group, [&](auto g) {
+    hipLaunchKernelGGL((hsv::hsv_keygen_kernel<decltype(g)::value>), dim3(gr.blocks), dim3(hsv::kSignBlock), 0, stream,
+                       a, w, fault);
+  });
+  return ws.done(hipGetLastError());
 }
 
 extern "C" hipError_t hsv_launch_sign(const uint8_t *keys, uint32_t nkeys, const uint32_t *key_idx, const uint8_t *msg,
@@ -149,21 +137,18 @@ extern "C" hipError_t hsv_launch_sign(const uint8_t *keys, uint32_t nkeys, const
   if (m > (1u << 22)) return hipErrorInvalidValue;
   const int group = g_group.load();
   const Grid gr = grid_for(m, group);
-  void *ws = nullptr;
-  hipError_t e = hsv_ws_malloc(&ws, gr.ws_bytes, stream);
-  if (e != hipSuccess) return e;
+  hsv::Workspace ws(nullptr, 0, gr.ws_bytes, stream);
+  if (ws.status() != hipSuccess) return ws.status();
   const hsv::SignArgs a{keys, nkeys, key_idx, msg, msg_len, msg_stride, m, sig, sig_stride, comb16, hsv::kInjectNone, 0u};
-  uint32_t *w = static_cast<uint32_t *>(ws);
-  switch (group) {
-    case 1: launch_sign<1>(a, gr.blocks, w, fault, stream); break;
-    case 2: launch_sign<2>(a, gr.blocks, w, fault, stream); break;
-    case 4: launch_sign<4>(a, gr.blocks, w, fault, stream); break;
-    case 8: launch_sign<8>(a, gr.blocks, w, fault, stream); break;
-    default: launch_sign<16>(a, gr.blocks, w, fault, stream); break;
-  }
-  e = hipGetLastError();
-  const hipError_t ef = hipFreeAsync(ws, stream);
-  return e != hipSuccess ? e : ef;
+  uint32_t *w = reinterpret_cast<uint32_t *>(ws.get());
+  with_group(group, [&](auto g) {
+    constexpr int G = decltype(g)::value;
+    if (a.msg_len == 32)
+      hipLaunchKernelGGL((hsv::hsv_sign_kernel<G, true>), dim3(gr.blocks), dim3(hsv::kSignBlock), 0, stream, a, w, fault);
+    else
+      hipLaunchKernelGGL((hsv::hsv_sign_kernel<G, false>), dim3(gr.blocks), dim3(hsv::kSignBlock), 0, stream, a, w, fault);
+  });
+  return ws.done(hipGetLastError());
 }
 
 // Two launches on `stream`: the digests and slot statuses of the m transactions
@@ -177,25 +162,20 @@ extern "C" hipError_t hsv_launch_tx_sign(const uint8_t *keys, uint32_t nkeys, co
   const Grid gr = grid_for(m, group);
   // the signing workspace | m digests of 32 B | m status words
   const size_t off_dig = gr.ws_bytes, off_status = off_dig + (size_t)m * 32;
-  void *blk = nullptr;
-  hipError_t e = hsv_ws_malloc(&blk, off_status + (size_t)m * 4, stream);
-  if (e != hipSuccess) return e;
-  uint8_t *d = static_cast<uint8_t *>(blk);
+  hsv::Workspace ws(nullptr, 0, off_status + (size_t)m * 4, stream);
+  if (ws.status() != hipSuccess) return ws.status();
+  uint8_t *d = ws.get();
   uint32_t *status = reinterpret_cast<uint32_t *>(d + off_status);
-  e = hsv_launch_tx_digest(txs, offsets, tx_size, key_idx, nkeys, m, d + off_dig, status, stream);
+  hipError_t e = hsv_launch_tx_digest(txs, offsets, tx_size, key_idx, nkeys, m, d + off_dig, status, stream);
   if (e == hipSuccess) {
     const hsv::SignArgs a{keys, nkeys, key_idx, d + off_dig, 32, 32, m, nullptr, 0, comb16, hsv::kInjectNone, 0u};
     const hsv::TxSignIo io{status, txs, offsets, tx_size};
-    uint32_t *w = static_cast<uint32_t *>(blk);
-    switch (group) {
-      case 1: launch_tx_sign<1>(a, io, gr.blocks, w, fault, stream); break;
-      case 2: launch_tx_sign<2>(a, io, gr.blocks, w, fault, stream); break;
-      case 4: launch_tx_sign<4>(a, io, gr.blocks, w, fault, stream); break;
-      case 8: launch_tx_sign<8>(a, io, gr.blocks, w, fault, stream); break;
-      default: launch_tx_sign<16>(a, io, gr.blocks, w, fault, stream); break;
-    }
+    uint32_t *w = reinterpret_cast<uint32_t *>(d);
+    with_group(group, [&](auto g) {
+      hipLaunchKernelGGL((hsv::hsv_tx_sign_kernel<decltype(g)::value>), dim3(gr.blocks), dim3(hsv::kSignBlock), 0,
+                         stream, a, io, w, fault);
+    });
     e = hipGetLastError();
   }
-  const hipError_t ef = hipFreeAsync(blk, stream);
-  return e != hipSuccess ? e : ef;
+  return ws.done(e);
 }

@@ -51,8 +51,7 @@ int sign_args_ok(const hsv_signer *s, const uint32_t *key_idx, const void *msg, 
 }
 
 // ---- transactions (hsv_signer_sign_transactions*) -------------------------------
-constexpr size_t kTxSignChunkBytes = size_t(1) << 29;  // transaction bytes staged per launch of the host form
-std::atomic<size_t> g_tx_chunk{kChunk};                // items per launch (hsvi_set_tx_sign_chunk: tests)
+std::atomic<size_t> g_tx_chunk{kChunk};  // items per launch (hsvi_set_tx_sign_chunk: tests)
 
 // launches of at most g_tx_chunk items, one after the other on `stream`;
 // d_offsets are relative to d_txs, so a chunk only moves along the offsets
@@ -157,22 +156,11 @@ int hsv_signer_sign_device(const hsv_signer *s, const uint32_t *d_key_idx, const
   int rc = sign_args_ok(s, d_key_idx, d_msg, msg_len, msg_stride, m, d_sig);
   if (rc != HSV_OK) return rc;
   if (sig_stride < 64) return fail(HSV_ERR_INVALID_ARG, "signatures overlap");
-  rc = ensure_init();
+  DeviceCall call;
+  rc = call.begin(d_sig, stream, d_fault, DeviceCall::kWide, "signer", s->device);
   if (rc != HSV_OK) return rc;
-  const int pd = pointer_device(d_sig);
-  if (pd >= 0 && pd != s->device)
-    return fail(HSV_ERR_INVALID_ARG, "buffers live on device " + std::to_string(pd) + ", the signer on device " +
-                                         std::to_string(s->device));
-  DevCtx &c = ctx(s->device);
-  DeviceGuard guard(c.device);
-  if (guard.status() != hipSuccess) return hip_fail("hipSetDevice", guard.status());
-  rc = ensure_btable16(c);  // the B table is rebuilt if hsv_shutdown released it
-  if (rc != HSV_OK) return rc;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  uint32_t *fault = nullptr;
-  rc = call_fault_words(c, d_fault, st, &fault);
-  if (rc != HSV_OK) return rc;
-  const hipError_t e = sign_chunks(*s, d_key_idx, d_msg, msg_len, msg_stride, m, d_sig, sig_stride, c.d_btable16, fault, st);
+  const hipError_t e = sign_chunks(*s, d_key_idx, d_msg, msg_len, msg_stride, m, d_sig, sig_stride, call.comb,
+                                   call.fault, call.stream);
   return e == hipSuccess ? HSV_OK : hip_fail("sign kernel launch", e);
 }
 
@@ -192,30 +180,19 @@ int hsv_signer_sign(hsv_signer *s, const uint32_t *key_idx, const uint8_t *msgs,
   Slot &slot = lease.slot();
   rc = slot_prepare(slot, 0, 0);
   if (rc != HSV_OK) return rc;
-  hipStream_t st = slot.stream;
-  // one stream-ordered block from the library pool: signatures | fault words | key indices | messages
-  const size_t msg_bytes = msg_stride ? (m - 1) * msg_stride + msg_len : msg_len;
-  const size_t off_fault = m * 64, off_idx = off_fault + 256, off_msg = off_idx + round_up(key_idx ? m * 4 : 0, 256);
-  void *blk = nullptr;
-  hipError_t e = hsv_ws_malloc(&blk, off_msg + msg_bytes + 256, st);
-  if (e != hipSuccess) return hip_fail("allocating the signing buffers", e);
-  uint8_t *d = static_cast<uint8_t *>(blk);
-  uint32_t *d_fault = reinterpret_cast<uint32_t *>(d + off_fault);
-  uint32_t *d_idx = key_idx ? reinterpret_cast<uint32_t *>(d + off_idx) : nullptr;
-  uint8_t words[kFaultBytes] = {0};
-  e = hipMemsetAsync(d_fault, 0, kFaultBytes, st);
-  if (e == hipSuccess && key_idx) e = hipMemcpyAsync(d_idx, key_idx, m * 4, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && msg_bytes) e = hipMemcpyAsync(d + off_msg, msgs, msg_bytes, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess)
-    e = sign_chunks(*s, d_idx, d + off_msg, msg_len, msg_stride, m, d, 64, c.d_btable16, d_fault, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(sig_out, d, m * 64, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(words, d_fault, kFaultBytes, hipMemcpyDeviceToHost, st);
-  const hipError_t ef = hipFreeAsync(blk, st);
-  const hipError_t es = hipStreamSynchronize(st);
-  if (e == hipSuccess) e = ef;
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return hip_fail("hsv_signer_sign", e);
-  return check_faults(words, "hsv_signer_sign");
+  const size_t msg_bytes = BatchSpan{nullptr, msg_stride, msg_len}.span_bytes(0, m);
+  StagedBlock blk(slot.stream);
+  const size_t off_sig = blk.add(m * 64), off_idx = blk.add(key_idx ? m * 4 : 0), off_msg = blk.add(msg_bytes);
+  rc = blk.alloc("allocating the signing buffers");
+  if (rc != HSV_OK) return rc;
+  uint32_t *d_idx = key_idx ? reinterpret_cast<uint32_t *>(blk.at(off_idx)) : nullptr;
+  if (key_idx) blk.in(off_idx, key_idx, m * 4);
+  blk.in(off_msg, msgs, msg_bytes);
+  if (blk.ok())
+    blk.step(sign_chunks(*s, d_idx, blk.at(off_msg), msg_len, msg_stride, m, blk.at(off_sig), 64, c.d_btable16,
+                         blk.fault(), slot.stream));
+  blk.out(sig_out, off_sig, m * 64);
+  return blk.finish("hsv_signer_sign");
 }
 
 int hsv_signer_sign_transactions_device(const hsv_signer *s, const uint32_t *d_key_idx, uint8_t *d_txs,
@@ -227,31 +204,11 @@ int hsv_signer_sign_transactions_device(const hsv_signer *s, const uint32_t *d_k
   if (reinterpret_cast<uintptr_t>(d_offsets) & 7u) return fail(HSV_ERR_ALIGN, "d_offsets must be 8-byte aligned");
   if (!d_offsets && tx_size < 96) return fail(HSV_ERR_INVALID_ARG, "transactions are shorter than 96 bytes");
   if (n > 0xffffffffu) return fail(HSV_ERR_INVALID_ARG, "batch too large");
-  int rc = ensure_init();
+  DeviceCall call;
+  const int rc = call.begin(d_txs, stream, d_fault, DeviceCall::kWide, "signer", s->device);
   if (rc != HSV_OK) return rc;
   if (!d_key_idx && n > s->n) return fail(HSV_ERR_INVALID_ARG, "more items than keys and no key_idx");
-  // the buffers and the stream are on the signer's device
-  const int pd = pointer_device(d_txs);
-  if (pd >= 0 && pd != s->device)
-    return fail(HSV_ERR_INVALID_ARG, "buffers live on device " + std::to_string(pd) + ", the signer on device " +
-                                         std::to_string(s->device));
-  if (stream) {
-    int sd = -1;
-    if (hipStreamGetDevice(reinterpret_cast<hipStream_t>(stream), &sd) == hipSuccess && sd >= 0 && sd != s->device)
-      return fail(HSV_ERR_INVALID_ARG, "the stream belongs to device " + std::to_string(sd) +
-                                           ", the signer to device " + std::to_string(s->device));
-    (void)hipGetLastError();
-  }
-  DevCtx &c = ctx(s->device);
-  DeviceGuard guard(c.device);
-  if (guard.status() != hipSuccess) return hip_fail("hipSetDevice", guard.status());
-  rc = ensure_btable16(c);  // the B table is rebuilt if hsv_shutdown released it
-  if (rc != HSV_OK) return rc;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  uint32_t *fault = nullptr;
-  rc = call_fault_words(c, d_fault, st, &fault);
-  if (rc != HSV_OK) return rc;
-  const hipError_t e = tx_sign_chunks(*s, d_key_idx, d_txs, d_offsets, tx_size, n, c.d_btable16, fault, st);
+  const hipError_t e = tx_sign_chunks(*s, d_key_idx, d_txs, d_offsets, tx_size, n, call.comb, call.fault, call.stream);
   return e == hipSuccess ? HSV_OK : hip_fail("transaction sign launch", e);
 }
 
@@ -260,14 +217,9 @@ int hsv_signer_sign_transactions(hsv_signer *s, const uint32_t *key_idx, uint8_t
   if (n == 0) return HSV_OK;
   if (!s || !txs) return fail(HSV_ERR_INVALID_ARG, "null argument");
   if (n > 0xffffffffu) return fail(HSV_ERR_INVALID_ARG, "batch too large");
-  if (offsets) {  // the length check of hsv_verify_transactions
-    for (size_t i = 0; i < n; ++i)
-      if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] < 96)
-        return fail(HSV_ERR_INVALID_ARG, "transaction " + std::to_string(i) + " is shorter than 96 bytes");
-  } else if (tx_size < 96) {
-    return fail(HSV_ERR_INVALID_ARG, "transactions are shorter than 96 bytes");
-  }
-  int rc = ensure_init();
+  int rc = tx_lengths_ok(offsets, tx_size, n);  // the length check of hsv_verify_transactions
+  if (rc != HSV_OK) return rc;
+  rc = ensure_init();
   if (rc != HSV_OK) return rc;
   if (!key_idx && n > s->n) return fail(HSV_ERR_INVALID_ARG, "more items than keys and no key_idx");
   DevCtx &c = ctx(s->device);
@@ -280,63 +232,44 @@ int hsv_signer_sign_transactions(hsv_signer *s, const uint32_t *key_idx, uint8_t
   rc = slot_prepare(slot, 0, 0);
   if (rc != HSV_OK) return rc;
   hipStream_t st = slot.stream;
-  const size_t per_launch = g_tx_chunk.load();
+  const BatchSpan span{offsets, tx_size, tx_size};
   std::vector<uint64_t> rel;  // a chunk's offsets, relative to its first byte
   std::vector<uint8_t> back;  // a ragged chunk as the device left it
-  for (size_t a = 0; a < n;) {
-    // items [a, b): at most one launch, and at most kTxSignChunkBytes unless one transaction is longer
-    size_t b = a + 1;
-    if (!offsets) {
-      b = std::min(n, a + std::min(per_launch, std::max<size_t>(1, kTxSignChunkBytes / tx_size)));
-    } else {
-      while (b < n && b - a < per_launch && offsets[b + 1] - offsets[a] <= kTxSignChunkBytes) ++b;
-    }
-    const size_t m = b - a;
-    const size_t first = offsets ? (size_t)offsets[a] : a * tx_size;
-    const size_t bytes = offsets ? (size_t)(offsets[b] - offsets[a]) : m * tx_size;
-    // one stream-ordered block from the library pool: fault words | key indices | offsets | transactions
-    const size_t off_idx = kAlign, off_offs = off_idx + round_up(key_idx ? m * 4 : 0, kAlign);
-    const size_t off_tx = off_offs + round_up(offsets ? (m + 1) * 8 : 0, kAlign);
-    void *blk = nullptr;
-    hipError_t e = hsv_ws_malloc(&blk, off_tx + bytes + kAlign, st);
-    if (e != hipSuccess) return hip_fail("allocating the transaction signing buffers", e);
-    uint8_t *d = static_cast<uint8_t *>(blk);
-    uint32_t *d_fault = reinterpret_cast<uint32_t *>(d);
-    uint32_t *d_idx = key_idx ? reinterpret_cast<uint32_t *>(d + off_idx) : nullptr;
-    uint64_t *d_offs = offsets ? reinterpret_cast<uint64_t *>(d + off_offs) : nullptr;
-    uint8_t words[kFaultBytes] = {0};
-    e = hipMemsetAsync(d_fault, 0, kFaultBytes, st);
-    if (e == hipSuccess && key_idx) e = hipMemcpyAsync(d_idx, key_idx + a, m * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && offsets) {
+  for (size_t a = 0, b; a < n; a = b) {
+    b = span.chunk_end(a, n, g_tx_chunk.load(), g_stage_bytes.load());  // one launch
+    const size_t m = b - a, first = span.first_byte(a), bytes = span.span_bytes(a, b);
+    StagedBlock blk(st);
+    const size_t off_idx = blk.add(key_idx ? m * 4 : 0), off_offs = blk.add(offsets ? (m + 1) * 8 : 0);
+    const size_t off_tx = blk.add(bytes);
+    rc = blk.alloc("allocating the transaction signing buffers");
+    if (rc != HSV_OK) return rc;
+    uint32_t *d_idx = key_idx ? reinterpret_cast<uint32_t *>(blk.at(off_idx)) : nullptr;
+    uint64_t *d_offs = offsets ? reinterpret_cast<uint64_t *>(blk.at(off_offs)) : nullptr;
+    if (key_idx) blk.in(off_idx, key_idx + a, m * 4);
+    if (offsets) {
       rel.resize(m + 1);
-      for (size_t k = 0; k <= m; ++k) rel[k] = offsets[a + k] - offsets[a];
-      e = hipMemcpyAsync(d_offs, rel.data(), (m + 1) * 8, hipMemcpyHostToDevice, st);
+      span.rel_offsets(a, b, rel.data());
+      blk.in(off_offs, rel.data(), (m + 1) * 8);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(d + off_tx, txs + first, bytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
+    blk.in(off_tx, txs + first, bytes);
+    if (blk.ok()) {
       const size_t kb = std::min(a, s->n);  // key_idx == NULL: item i uses key i
-      e = hsv_launch_tx_sign(s->d_keys + (key_idx ? 0 : kb * 96), (uint32_t)(key_idx ? s->n : s->n - kb), d_idx,
-                             d + off_tx, d_offs, tx_size, (uint32_t)m, c.d_btable16, d_fault, st);
+      blk.step(hsv_launch_tx_sign(s->d_keys + (key_idx ? 0 : kb * 96), (uint32_t)(key_idx ? s->n : s->n - kb), d_idx,
+                                  blk.at(off_tx), d_offs, tx_size, (uint32_t)m, c.d_btable16, blk.fault(), st));
     }
     // only the tails come back: the caller's message bytes are never written
-    if (e == hipSuccess && !offsets)
-      e = hipMemcpy2DAsync(txs + first + (tx_size - 96), tx_size, d + off_tx + (tx_size - 96), tx_size, 96, m,
-                           hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && offsets) {
+    if (blk.ok() && !offsets)
+      blk.step(hipMemcpy2DAsync(txs + first + (tx_size - 96), tx_size, blk.at(off_tx) + (tx_size - 96), tx_size, 96, m,
+                                hipMemcpyDeviceToHost, st));
+    if (offsets) {
       back.resize(bytes);
-      e = hipMemcpyAsync(back.data(), d + off_tx, bytes, hipMemcpyDeviceToHost, st);
+      blk.out(back.data(), off_tx, bytes);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(words, d_fault, kFaultBytes, hipMemcpyDeviceToHost, st);
-    const hipError_t ef = hipFreeAsync(blk, st);
-    const hipError_t es = hipStreamSynchronize(st);  // nothing of this call stays in flight
-    if (e == hipSuccess) e = ef;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return hip_fail("hsv_signer_sign_transactions", e);
-    if (offsets)
+    const bool copied = blk.ok();
+    rc = blk.finish("hsv_signer_sign_transactions");
+    if (offsets && copied && (rc == HSV_OK || rc == HSV_ERR_DEVICE_FAULT))
       for (size_t k = 0; k < m; ++k) std::memcpy(txs + first + rel[k + 1] - 96, back.data() + rel[k + 1] - 96, 96);
-    rc = check_faults(words, "hsv_signer_sign_transactions");
     if (rc != HSV_OK) return rc;
-    a = b;
   }
   return HSV_OK;
 }

@@ -8,7 +8,6 @@
 #include <cstring>
 #include <string>
 #include <thread>
-#include <utility>
 #include <vector>
 
 #include "hsv.h"
@@ -17,8 +16,6 @@
 
 namespace hsvh {
 namespace {
-
-constexpr size_t kTxChunkBytes = size_t(1) << 29;  // transaction bytes staged per launch
 
 // records, verification and the short-transaction mask for m <= kChunk
 // transactions already in HBM (d_offsets relative to d_txs, or NULL = fixed size)
@@ -32,29 +29,30 @@ int tx_enqueue(int v, const uint32_t *comb_b, const uint8_t *d_txs, const uint64
   return HSV_OK;
 }
 
-size_t tx_bytes(const uint64_t *offsets, size_t tx_size, size_t a, size_t b) {
-  return offsets ? (size_t)(offsets[b] - offsets[a]) : (b - a) * tx_size;
+}  // namespace
+
+// "transaction i is shorter than 96 bytes" for the first such i of a ragged
+// batch (or one whose offsets decrease), or for a fixed size below 96
+int tx_lengths_ok(const uint64_t *offsets, size_t tx_size, size_t n) {
+  if (!offsets)
+    return tx_size < 96 ? fail(HSV_ERR_INVALID_ARG, "transactions are shorter than 96 bytes") : HSV_OK;
+  const size_t bad = first_bad_item(offsets, n, 96);
+  return bad == n ? HSV_OK
+                  : fail(HSV_ERR_INVALID_ARG, "transaction " + std::to_string(bad) + " is shorter than 96 bytes");
 }
+
+namespace {
 
 // transactions [lo, hi) of the caller's arrays on device c, chunk by chunk
 int run_tx_on_device(DevCtx &c, const uint8_t *txs, const uint64_t *offsets, size_t tx_size, size_t lo, size_t hi,
                      uint8_t *flags_out) {
-  std::vector<std::pair<size_t, size_t>> chunks;
+  const BatchSpan span{offsets, tx_size, tx_size};
+  std::vector<size_t> ends;  // the chunks' ends, in order from lo
   size_t max_items = 0, max_bytes = 0;
-  if (!offsets) {
-    const size_t per = std::max<size_t>(1, std::min(kChunk, kTxChunkBytes / tx_size));
-    for (size_t a = lo; a < hi; a += per) chunks.emplace_back(a, std::min(hi, a + per));
-  } else {
-    for (size_t a = lo; a < hi;) {
-      size_t b = a + 1;
-      while (b < hi && b - a < kChunk && tx_bytes(offsets, 0, a, b + 1) <= kTxChunkBytes) ++b;
-      chunks.emplace_back(a, b);
-      a = b;
-    }
-  }
-  for (auto &ch : chunks) {
-    max_items = std::max(max_items, ch.second - ch.first);
-    max_bytes = std::max(max_bytes, tx_bytes(offsets, tx_size, ch.first, ch.second));
+  for (size_t a = lo; a < hi; a = ends.back()) {
+    ends.push_back(span.chunk_end(a, hi, kChunk, g_stage_bytes.load()));
+    max_items = std::max(max_items, ends.back() - a);
+    max_bytes = std::max(max_bytes, span.span_bytes(a, ends.back()));
   }
   // device: tx bytes | offsets | records | flags | self-check words;
   // host: tx bytes | offsets | flags | self-check words
@@ -76,16 +74,14 @@ int run_tx_on_device(DevCtx &c, const uint8_t *txs, const uint64_t *offsets, siz
   Slot &s = lease.slot();
   rc = slot_prepare(s, d_total, h_total);
   if (rc != HSV_OK) return rc;
-  for (auto &ch : chunks) {
-    const size_t a = ch.first, m = ch.second - ch.first;
-    const size_t bytes = tx_bytes(offsets, tx_size, a, ch.second);
-    const size_t first = offsets ? (size_t)offsets[a] : a * tx_size;
+  size_t a = lo;
+  for (const size_t b : ends) {
+    const size_t m = b - a, bytes = span.span_bytes(a, b);
     uint8_t *h = s.h_buf;
-    stage_copy(h, txs + first, bytes);
+    stage_copy(h, txs + span.first_byte(a), bytes);
     size_t in_bytes = bytes;
     if (offsets) {
-      uint64_t *ho = reinterpret_cast<uint64_t *>(h + off_off);
-      for (size_t k = 0; k <= m; ++k) ho[k] = offsets[a + k] - offsets[a];
+      span.rel_offsets(a, b, reinterpret_cast<uint64_t *>(h + off_off));
       in_bytes = off_off + (m + 1) * 8;
     }
     hipError_t e = hipMemcpyAsync(s.d_buf, h, in_bytes, hipMemcpyHostToDevice, s.stream);
@@ -109,6 +105,7 @@ int run_tx_on_device(DevCtx &c, const uint8_t *txs, const uint64_t *offsets, siz
     rc = check_faults(h + h_fault_off, "transaction verify");
     if (rc != HSV_OK) return rc;
     std::memcpy(flags_out + (a - lo), h + h_flag_off, m);
+    a = b;
   }
   return HSV_OK;
 }
@@ -116,14 +113,9 @@ int run_tx_on_device(DevCtx &c, const uint8_t *txs, const uint64_t *offsets, siz
 int run_tx_host(const uint8_t *txs, const uint64_t *offsets, size_t tx_size, size_t n, uint8_t *flags_out) {
   if (n == 0) return HSV_OK;
   if (!txs || !flags_out) return fail(HSV_ERR_INVALID_ARG, "null pointer");
-  if (offsets) {
-    for (size_t i = 0; i < n; ++i)
-      if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] < 96)
-        return fail(HSV_ERR_INVALID_ARG, "transaction " + std::to_string(i) + " is shorter than 96 bytes");
-  } else if (tx_size < 96) {
-    return fail(HSV_ERR_INVALID_ARG, "transactions are shorter than 96 bytes");
-  }
-  int rc = ensure_init();
+  int rc = tx_lengths_ok(offsets, tx_size, n);
+  if (rc != HSV_OK) return rc;
+  rc = ensure_init();
   if (rc != HSV_OK) return rc;
   const int k = shard_count(n);
   if (k <= 1) return run_tx_on_device(ctx(home_device()), txs, offsets, tx_size, 0, n, flags_out);
@@ -158,30 +150,19 @@ int hsv_verify_transactions_device(const uint8_t *d_txs, const uint64_t *d_offse
   if (!d_txs) return fail(HSV_ERR_INVALID_ARG, "null d_txs");
   if (!d_flags && !d_strict_bits) return fail(HSV_ERR_INVALID_ARG, "no output");
   if (!d_offsets && tx_size < 96) return fail(HSV_ERR_INVALID_ARG, "transactions are shorter than 96 bytes");
-  int rc = ensure_init();
+  DeviceCall call;
+  int rc = call.begin(d_txs, stream, d_fault, DeviceCall::kVariant);
   if (rc != HSV_OK) return rc;
-  int dev = 0;
-  rc = device_for_call(d_txs, stream, &dev);
-  if (rc != HSV_OK) return rc;
-  DeviceGuard guard(dev);
-  if (guard.status() != hipSuccess) return hip_fail("hipSetDevice", guard.status());
-  const int v = variant();
-  const uint32_t *comb_b = nullptr;
-  rc = comb_table_for(ctx(dev), v, &comb_b);
-  if (rc != HSV_OK) return rc;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  uint32_t *fault = nullptr;
-  rc = call_fault_words(ctx(dev), d_fault, s, &fault);
-  if (rc != HSV_OK) return rc;
+  hipStream_t s = call.stream;
   const size_t per = std::min(n, kChunk);
   void *rec = nullptr;
   hipError_t e = hsv_ws_malloc(reinterpret_cast<void **>(&rec), per * 128, s);
   if (e != hipSuccess) return hip_fail("workspace allocation (transaction records)", e);
   for (size_t base = 0; base < n && rc == HSV_OK; base += per) {
     const size_t m = std::min(per, n - base);
-    rc = tx_enqueue(v, comb_b, d_offsets ? d_txs : d_txs + base * tx_size, d_offsets ? d_offsets + base : nullptr,
+    rc = tx_enqueue(call.v, call.comb, d_offsets ? d_txs : d_txs + base * tx_size, d_offsets ? d_offsets + base : nullptr,
                     tx_size, m, static_cast<uint8_t *>(rec), d_flags ? d_flags + base : nullptr,
-                    d_strict_bits ? d_strict_bits + base / 32 : nullptr, fault, s);
+                    d_strict_bits ? d_strict_bits + base / 32 : nullptr, call.fault, s);
   }
   e = hipFreeAsync(rec, s);
   if (rc != HSV_OK) return rc;

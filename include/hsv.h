@@ -267,8 +267,9 @@ HSV_API int hsv_committee_verify(hsv_committee *c, const uint32_t *key_idx, cons
  * cached tables, any other key the generic kernel.  1 = Ok, 0 = Err, < 0 error. */
 HSV_API int hsv_committee_verify_batch_packed(hsv_committee *c, const uint8_t digest[32], const uint8_t *votes,
                                       size_t m);
-/* Device-resident, stream-ordered form (device = the committee's); d_fault
- * (optional) as hsv_verify_device_bits. */
+/* Device-resident, stream-ordered form (device = the committee's: buffers or
+ * a stream of another device are HSV_ERR_INVALID_ARG, and nothing is
+ * enqueued); d_fault (optional) as hsv_verify_device_bits. */
 HSV_API int hsv_committee_verify_device(const hsv_committee *c, const uint32_t *d_key_idx, const uint8_t *d_sig,
                                 size_t sig_stride, const uint8_t *d_msg, size_t msg_stride, size_t m,
                                 uint8_t *d_flags, uint32_t *d_fault, void *stream);
@@ -361,8 +362,9 @@ HSV_API int hsv_signer_public_keys(const hsv_signer *s, uint8_t *pk_out);
  * signature and returns HSV_ERR_DEVICE_FAULT. */
 HSV_API int hsv_signer_sign(hsv_signer *s, const uint32_t *key_idx, const uint8_t *msgs, size_t msg_len,
                             size_t msg_stride, size_t m, uint8_t *sig_out);
-/* Device-resident, stream-ordered form (device = the signer's; no
- * synchronisation): item i's signature goes to d_sig + i*sig_stride, so
+/* Device-resident, stream-ordered form (device = the signer's: buffers or a
+ * stream of another device are HSV_ERR_INVALID_ARG, and nothing is enqueued;
+ * no synchronisation): item i's signature goes to d_sig + i*sig_stride, so
  * sig_stride 96 with d_sig = records + 32 fills packed pk||R||s vote records.
  * d_sig and sig_stride must be multiples of 16 (HSV_ERR_ALIGN); d_msg may have
  * any alignment.  d_fault (optional) as hsv_verify_device_bits (only

@@ -56,6 +56,16 @@ def test_chunk_hook_is_a_test_library_export_only(lib):
     assert t.hsv_test_tx_sign_chunk(0) == 300 and t.hsv_test_tx_sign_chunk(0) == 1 << 22
 
 
+def test_stage_bytes_hook_is_a_test_library_export_only(lib):
+    from hsverify import _lib
+    assert "hsv_test_stage_bytes" in _lib.HOOKS
+    assert getattr(lib, "hsv_test_stage_bytes", None) is None or _lib.LIB_PATH == _lib.TEST_LIB_PATH
+    t = _lib.load_test()
+    prev = t.hsv_test_stage_bytes(4096)
+    assert prev == 1 << 29                       # the product's bytes per launch
+    assert t.hsv_test_stage_bytes(0) == 4096 and t.hsv_test_stage_bytes(0) == 1 << 29
+
+
 def test_python_layer_exports():
     from hsverify import Signer, synth
     assert callable(Signer.sign_transactions) and callable(Signer.sign_transactions_device)

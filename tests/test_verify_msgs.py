@@ -331,3 +331,29 @@ def test_agrees_with_the_32_byte_path(hsv):
         out.append((flags.cpu().numpy(), bits.cpu().numpy()))
     assert (out[0][0] == out[1][0]).all() and (out[0][1] == out[1][1]).all()
     assert ((out[0][0] & o.STRICT_OK) != 0).tolist() == w.accept.tolist()
+
+
+def test_host_form_across_its_byte_cap(hsv, oracle_lib, ragged):
+    """The host form stages at most 2^29 message bytes per launch; the test
+    library's hsv_test_stage_bytes lowers that to 4096.  The 257 ragged,
+    unaligned messages then take a dozen launches, each with its offsets
+    rebased to its first byte, and one message of 5000 bytes -- longer than
+    the cap -- goes alone.  Flags equal the oracle's, and those of the same
+    call at the product's cap."""
+    from hsverify import _testing, verifier
+    at = 100
+    long = np.random.default_rng(57).integers(0, 256, 5000, dtype=np.uint8).tobytes()
+    pk, sig, msgs, exp = ragged["pk"].copy(), ragged["sig"].copy(), list(ragged["msgs"]), ragged["exp"].copy()
+    pk[at:at + 1], sig[at:at + 1] = sign_ragged(np.full((1, 32), 9, np.uint8), [long])
+    msgs[at] = long
+    exp[at] = oracle_msgs(oracle_lib, pk[at:at + 1], sig[at:at + 1], [long])[0]
+    assert exp[at] & o.STRICT_OK and 0 < (exp & o.STRICT_OK).sum() < len(msgs)
+    with _testing.test_library() as lib:
+        whole = verifier.verify_msgs(pk, sig, msgs)
+        assert lib.hsv_test_stage_bytes(4096) == 1 << 29
+        try:
+            got = verifier.verify_msgs(pk, sig, msgs)
+        finally:
+            assert lib.hsv_test_stage_bytes(0) == 4096
+    assert (got == exp).all(), np.nonzero(got != exp)[0][:8]
+    assert (got == whole).all()
