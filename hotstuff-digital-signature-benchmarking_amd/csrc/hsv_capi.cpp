@@ -737,6 +737,11 @@ int DeviceCall::begin(const void *d_ptr, void *stream_in, uint32_t *d_fault, Tab
   if (table == kVariant) {
     v = variant();
     rc = comb_table_for(*c, v, &comb);
+  } else if (table == kBoth) {
+    rc = ensure_btable(*c);
+    if (rc == HSV_OK) rc = ensure_btable16(*c);
+    comb = c->d_btable;
+    comb16 = c->d_btable16;
   } else {  // rebuilt here if hsv_shutdown released it
     rc = table == kNarrow ? ensure_btable(*c) : ensure_btable16(*c);
     comb = table == kNarrow ? c->d_btable : c->d_btable16;

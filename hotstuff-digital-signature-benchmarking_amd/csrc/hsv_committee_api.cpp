@@ -28,6 +28,7 @@
 #include "hsv.h"
 #include "hsv_host.h"
 #include "hsv_internal.h"
+#include "hsv_keytab.hpp"
 
 namespace hsvh {
 namespace {
@@ -610,6 +611,10 @@ struct hsv_committee {
   uint8_t *d_kflags = nullptr;
   uint32_t *d_tables = nullptr;
   uint32_t **d_tabptr = nullptr;
+  // member index by key bytes on the device (hsv_keytab.hpp), built with the
+  // tables; read by hsv_committee_verify_transactions* only
+  uint32_t *d_keytab = nullptr;
+  uint32_t keymask = 0;
   KeyIndex index;
 };
 
@@ -636,7 +641,10 @@ int hsv_committee_create(const uint8_t *pks, size_t n, hsv_committee **out) {
     uint32_t *d_tmp = nullptr;
     hipStream_t st = nullptr;
     std::vector<uint32_t *> ptrs(n);
+    const std::vector<uint32_t> keytab = hsv::keytab_build(pks, n, KeyHash::seed());
+    cm->keymask = (uint32_t)keytab.size() - 1u;
     hipError_t e = hipMalloc(&cm->d_pks, n * 32);
+    if (e == hipSuccess) e = hipMalloc(&cm->d_keytab, keytab.size() * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMalloc(&cm->d_kflags, n);
     if (e == hipSuccess) e = hipMalloc(&cm->d_tables, n * hsv_comb_table_bytes());
     if (e == hipSuccess) e = hipMalloc(&cm->d_tabptr, n * sizeof(uint32_t *));
@@ -646,6 +654,8 @@ int hsv_committee_create(const uint8_t *pks, size_t n, hsv_committee **out) {
     if (e == hipSuccess) e = hipMemcpyAsync(cm->d_pks, pks, n * 32, hipMemcpyHostToDevice, st);
     if (e == hipSuccess)
       e = hipMemcpyAsync(cm->d_tabptr, ptrs.data(), n * sizeof(uint32_t *), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(cm->d_keytab, keytab.data(), keytab.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
     if (e == hipSuccess)
       e = build_tables(cm->d_pks, (uint32_t)n, ptrs.data(), cm->d_kflags, d_tmp, std::min<uint32_t>((uint32_t)n, 1024), st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -674,6 +684,7 @@ void hsv_committee_destroy(hsv_committee *cm) {
   if (cm->d_kflags) (void)hipFree(cm->d_kflags);
   if (cm->d_tables) (void)hipFree(cm->d_tables);
   if (cm->d_tabptr) (void)hipFree(cm->d_tabptr);
+  if (cm->d_keytab) (void)hipFree(cm->d_keytab);
   delete cm;
 }
 
@@ -729,6 +740,172 @@ int hsv_committee_verify_batch_packed(hsv_committee *cm, const uint8_t digest[32
   }
   const int rc = committee_run(cm->dev, idx.data(), votes + 32, 96, digest, 0, m, flags.data());
   return rc != HSV_OK ? rc : batch_verdict(flags.data(), m);
+}
+
+}  // extern "C"
+
+// ---- mempool transactions of known signers -------------------------------------------
+// hsv_committee_verify_transactions*: the transaction layout and scheme of
+// hsv_verify_transactions* (hsv_tx.cpp), with the signer looked up on the
+// device (hsv_keytab.hpp): a member's transaction takes its comb table, any
+// other the generic point pass -- three launches per round of at most kChunk
+// transactions (hsv_launch_committee_tx, hsv_mempool.hip), no host round trip.
+namespace hsvh {
+namespace {
+
+// the list-length slot of the calling thread's last call (committee_tx_counts)
+struct TxCountRef {
+  int device = -1;
+  unsigned slot = 0;
+};
+thread_local TxCountRef t_tx_counts;
+
+// Takes the next slot of device c (current) for this call and zeroes it on
+// `stream`; out: the slot's three 64-bit words.
+int tx_counts_begin(DevCtx &c, hipStream_t stream, uint64_t **out) {
+  uint32_t *words = nullptr;
+  const int rc = device_fault_words(c, &words);
+  if (rc != HSV_OK) return rc;
+  const unsigned slot = c.tx_count_rr.fetch_add(1) % kTxCountSlots;
+  uint8_t *p = reinterpret_cast<uint8_t *>(words) + kTxCountOff + slot * kTxCountBytes;
+  const hipError_t e = hipMemsetAsync(p, 0, kTxCountBytes, stream);
+  if (e != hipSuccess) return hip_fail("zeroing the call's list lengths", e);
+  t_tx_counts.device = c.device;
+  t_tx_counts.slot = slot;
+  *out = reinterpret_cast<uint64_t *>(p);
+  return HSV_OK;
+}
+
+// n transactions already in HBM, in rounds of kChunk in order on `stream`
+// (d_offsets relative to d_txs, or NULL = fixed size)
+int committee_tx_enqueue(const hsv_committee &cm, const uint32_t *btable, const uint32_t *comb16, const uint8_t *d_txs,
+                         const uint64_t *d_offsets, size_t tx_size, size_t n, uint8_t *d_flags, uint32_t *d_bits,
+                         uint32_t *d_fault, uint64_t *d_totals, hipStream_t s) {
+  for (size_t base = 0; base < n; base += kChunk) {
+    const size_t m = std::min(kChunk, n - base);
+    const hipError_t e = hsv_launch_committee_tx(
+        d_offsets ? d_txs : d_txs + base * tx_size, d_offsets ? d_offsets + base : nullptr, tx_size, (uint32_t)m,
+        cm.d_keytab, cm.keymask, KeyHash::seed(), cm.dev.d_pks, cm.dev.d_kflags, cm.dev.n, cm.dev.d_tabptr, btable,
+        comb16, d_flags ? d_flags + base : nullptr, d_bits ? d_bits + base / 32 : nullptr, d_fault, d_totals, s);
+    if (e != hipSuccess) return hip_fail("committee transaction launch", e);
+  }
+  return HSV_OK;
+}
+
+// The host form: plain staged copies through a slot of the committee's
+// device, chunked as run_tx_on_device (hsv_tx.cpp); neither pipelined nor
+// sharded, the tables live on one device.
+int committee_tx_host(const hsv_committee &cm, const uint8_t *txs, const uint64_t *offsets, size_t tx_size, size_t n,
+                      uint8_t *flags_out) {
+  const BatchSpan span{offsets, tx_size, tx_size};
+  std::vector<size_t> ends;  // the chunks' ends, in order
+  size_t max_items = 0, max_bytes = 0;
+  for (size_t a = 0; a < n; a = ends.back()) {
+    ends.push_back(span.chunk_end(a, n, kChunk, g_stage_bytes.load()));
+    max_items = std::max(max_items, ends.back() - a);
+    max_bytes = std::max(max_bytes, span.span_bytes(a, ends.back()));
+  }
+  // device and host: tx bytes | offsets | flags | self-check words
+  const size_t off_off = round_up(max_bytes, kAlign);
+  const size_t flag_off = off_off + round_up((max_items + 1) * 8, kAlign);
+  const size_t fault_off = flag_off + round_up(max_items, kAlign);
+  const size_t total = fault_off + kAlign;
+  DevCtx &c = ctx(cm.dev.device);
+  DeviceGuard guard(c.device);
+  if (guard.status() != hipSuccess) return hip_fail("hipSetDevice", guard.status());
+  int rc = ensure_btable(c);
+  if (rc == HSV_OK) rc = ensure_btable16(c);
+  if (rc != HSV_OK) return rc;
+  SlotLease lease(c);
+  Slot &s = lease.slot();
+  rc = slot_prepare(s, total, total);
+  if (rc != HSV_OK) return rc;
+  uint64_t *d_totals = nullptr;
+  rc = tx_counts_begin(c, s.stream, &d_totals);
+  if (rc != HSV_OK) return rc;
+  size_t a = 0;
+  for (const size_t b : ends) {
+    const size_t m = b - a, bytes = span.span_bytes(a, b);
+    uint8_t *h = s.h_buf;
+    stage_copy(h, txs + span.first_byte(a), bytes);
+    size_t in_bytes = bytes;
+    if (offsets) {
+      span.rel_offsets(a, b, reinterpret_cast<uint64_t *>(h + off_off));
+      in_bytes = off_off + (m + 1) * 8;
+    }
+    hipError_t e = hipMemcpyAsync(s.d_buf, h, in_bytes, hipMemcpyHostToDevice, s.stream);
+    // unwritten flags read as rejections; self-check words start at zero
+    if (e == hipSuccess) e = hipMemsetAsync(s.d_buf + flag_off, 0, fault_off + kFaultBytes - flag_off, s.stream);
+    if (e != hipSuccess) {
+      (void)hipStreamSynchronize(s.stream);
+      return hip_fail("hipMemcpyAsync H2D", e);
+    }
+    rc = committee_tx_enqueue(cm, c.d_btable, c.d_btable16, s.d_buf,
+                              offsets ? reinterpret_cast<const uint64_t *>(s.d_buf + off_off) : nullptr, tx_size, m,
+                              s.d_buf + flag_off, nullptr, reinterpret_cast<uint32_t *>(s.d_buf + fault_off), d_totals,
+                              s.stream);
+    if (rc == HSV_OK) {
+      e = hipMemcpyAsync(h + flag_off, s.d_buf + flag_off, fault_off + kFaultBytes - flag_off, hipMemcpyDeviceToHost,
+                         s.stream);
+      if (e != hipSuccess) rc = hip_fail("hipMemcpyAsync D2H", e);
+    }
+    e = hipStreamSynchronize(s.stream);  // nothing of this call stays in flight
+    if (rc != HSV_OK) return rc;
+    if (e != hipSuccess) return hip_fail("hipStreamSynchronize", e);
+    rc = check_faults(h + fault_off, "committee transaction verify");
+    if (rc != HSV_OK) return rc;
+    std::memcpy(flags_out + a, h + flag_off, m);
+    a = b;
+  }
+  return HSV_OK;
+}
+
+}  // namespace
+
+int committee_tx_counts(uint64_t out[3]) {
+  if (!out) return fail(HSV_ERR_INVALID_ARG, "null argument");
+  if (t_tx_counts.device < 0) return fail(HSV_ERR_INVALID_ARG, "no committee transaction call on this thread");
+  DevCtx &c = ctx(t_tx_counts.device);
+  DeviceGuard guard(c.device);
+  uint32_t *words = nullptr;
+  const int rc = device_fault_words(c, &words);
+  if (rc != HSV_OK) return rc;
+  const hipError_t e = hipMemcpy(out, reinterpret_cast<uint8_t *>(words) + kTxCountOff + t_tx_counts.slot * kTxCountBytes,
+                                 3 * sizeof(uint64_t), hipMemcpyDeviceToHost);
+  return e == hipSuccess ? HSV_OK : hip_fail("hipMemcpy", e);
+}
+
+}  // namespace hsvh
+
+extern "C" {
+
+int hsv_committee_verify_transactions(hsv_committee *cm, const uint8_t *txs, const uint64_t *offsets, size_t tx_size,
+                                      size_t n, uint8_t *flags_out) {
+  CallScope call;
+  if (n == 0) return HSV_OK;
+  if (!cm || !txs || !flags_out) return fail(HSV_ERR_INVALID_ARG, "null argument");
+  int rc = tx_lengths_ok(offsets, tx_size, n);
+  if (rc != HSV_OK) return rc;
+  rc = ensure_init();
+  if (rc != HSV_OK) return rc;
+  return committee_tx_host(*cm, txs, offsets, tx_size, n, flags_out);
+}
+
+int hsv_committee_verify_transactions_device(const hsv_committee *cm, const uint8_t *d_txs, const uint64_t *d_offsets,
+                                             size_t tx_size, size_t n, uint8_t *d_flags, uint32_t *d_strict_bits,
+                                             uint32_t *d_fault, void *stream) {
+  if (n == 0) return HSV_OK;
+  if (!cm || !d_txs) return fail(HSV_ERR_INVALID_ARG, "null argument");
+  if (!d_flags && !d_strict_bits) return fail(HSV_ERR_INVALID_ARG, "no output");
+  if (!d_offsets && tx_size < 96) return fail(HSV_ERR_INVALID_ARG, "transactions are shorter than 96 bytes");
+  DeviceCall call;
+  int rc = call.begin(d_txs, stream, d_fault, DeviceCall::kBoth, "committee", cm->dev.device);
+  if (rc != HSV_OK) return rc;
+  uint64_t *d_totals = nullptr;
+  rc = tx_counts_begin(*call.c, call.stream, &d_totals);
+  if (rc != HSV_OK) return rc;
+  return committee_tx_enqueue(*cm, call.comb, call.comb16, d_txs, d_offsets, tx_size, n, d_flags, d_strict_bits,
+                              call.fault, d_totals, call.stream);
 }
 
 }  // extern "C"

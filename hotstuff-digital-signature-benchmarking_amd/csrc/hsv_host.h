@@ -136,6 +136,7 @@ struct DevCtx {
   std::mutex side_mu;                    // guards the side-stream pool
   std::vector<hipStream_t> side_free;    // idle second streams of multi-chunk device-API batches
   std::vector<hipStream_t> side_all;     // every side stream created (hsv_shutdown)
+  std::atomic<unsigned> tx_count_rr{0};  // next list-length slot of d_fault (committee_tx_counts)
 };
 
 // Makes `device` current for the calling thread and restores the previous
@@ -192,6 +193,10 @@ int check_faults(const uint8_t *words, const char *where);
 // must be c.device); allocated and zeroed on first use.
 int device_fault_words(DevCtx &c, uint32_t **out);
 constexpr size_t kFaultOutWord = 4;  // d_fault[4..5]: output of hsv_launch_fault_exchange
+// d_fault bytes [64, 256): kTxCountSlots slots of four 64-bit words, the list
+// lengths of the committee transaction calls (committee_tx_counts); a call
+// takes the next slot in turn
+constexpr size_t kTxCountSlots = 6, kTxCountOff = 64, kTxCountBytes = 32;
 // The words a device-API call reports into: the caller's d_fault (zeroed on
 // `stream` here), or the per-device words when d_fault is NULL.
 int call_fault_words(DevCtx &c, uint32_t *d_fault, hipStream_t stream, uint32_t **out);
@@ -295,13 +300,16 @@ int pointer_device(const void *p);
 // the handle in the error text).
 class DeviceCall {
  public:
-  enum Table { kNarrow, kWide, kVariant };  // ensure_btable, ensure_btable16, comb_table_for(variant())
+  // ensure_btable, ensure_btable16, comb_table_for(variant()); kBoth: the
+  // narrow table in `comb` and the wide one in `comb16`
+  enum Table { kNarrow, kWide, kVariant, kBoth };
   int begin(const void *d_ptr, void *stream, uint32_t *d_fault, Table table, const char *owner = nullptr,
             int owner_device = -1);
   DevCtx *c = nullptr;
   hipStream_t stream = nullptr;
   int v = 0;                       // variant() (kVariant only)
   const uint32_t *comb = nullptr;  // the table asked for
+  const uint32_t *comb16 = nullptr;  // kBoth: the wide table
   uint32_t *fault = nullptr;
 
  private:
@@ -333,6 +341,9 @@ void resident_quiesce();  // stop its kernel now (the next request relaunches it
 void resident_counts(uint64_t *posted, uint64_t *answered);
 int resident_post_bad(uint32_t m);  // test hook: a request the kernel must refuse
 int resident_set_mode(int on);      // hsv_set_resident_service
+// test hook (hsv_test_committee_tx_counts): hits, misses and fallback items of
+// the calling thread's last hsv_committee_verify_transactions* call
+int committee_tx_counts(uint64_t out[3]);
 
 // The generic host-buffer path (hsv_capi.cpp): records at the given strides.
 int run_host(const uint8_t *pk, size_t pk_stride, const uint8_t *sig, size_t sig_stride, const uint8_t *msg,

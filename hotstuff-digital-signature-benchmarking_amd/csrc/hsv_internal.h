@@ -64,6 +64,10 @@ int hsvi_set_inject(int mode);
 // Lattice bound of the comb-path prepass (tests; 0 = default); returns the
 // previous bound or -1.
 int hsvi_set_lattice_bits(int bits);
+// The bound in force, and a fresh canary nonce (odd, never 0): what launch_hp
+// hands its kernels, for the point-pass launcher of hsv_mempool.hip.
+int hsvi_lattice_bits(void);
+uint32_t hsvi_next_nonce(void);
 // Row-form field arithmetic against the one-lane form (hsv_committee.hip).
 int hsvi_lanesplit_check(const uint32_t *in, uint32_t rows, uint32_t *out);
 // Read-and-clear of two device fault words in one atomic exchange each, on
@@ -209,6 +213,20 @@ hipError_t hsv_launch_tx_fused(uint32_t grid, const uint8_t *txs, const uint64_t
 hipError_t hsv_launch_verify_tx(int variant, const uint8_t *txs, const uint64_t *offsets, uint64_t tx_size,
                                 uint32_t n, uint8_t *records, uint8_t *flags_out, uint32_t *strict_bits,
                                 const uint32_t *comb_b, uint32_t *fault, hipStream_t stream);
+// One round (n <= 2^22) of hsv_committee_verify_transactions*: the route
+// kernel (records, key lookup in keytab / keymask / seed over the committee's
+// pks, hit and miss lists, the misses' prepass), the comb pass over the hit
+// list (key_flags, key_tables, btable: the narrow comb of B) and the generic
+// pass over the miss list (comb16: the wide comb).  Every flag byte and strict
+// word of the round is written; fault as hsv_launch_verify.  totals (may be
+// NULL): three 64-bit device words that receive += {hits, misses, fallback
+// items}.  nkeys == 0: every transaction is a miss, the committee arrays may
+// be NULL.
+hipError_t hsv_launch_committee_tx(const uint8_t *txs, const uint64_t *offsets, uint64_t tx_size, uint32_t n,
+                                   const uint32_t *keytab, uint32_t keymask, uint64_t seed, const uint8_t *pks,
+                                   const uint8_t *key_flags, uint32_t nkeys, const uint32_t *const *key_tables,
+                                   const uint32_t *btable, const uint32_t *comb16, uint8_t *flags_out,
+                                   uint32_t *strict_bits, uint32_t *fault, uint64_t *totals, hipStream_t stream);
 // Ed25519 over messages of any length (hsv_verify_msgs*): k = SHA-512(R || A
 // || M) over the whole message.  Message i is msgs[offsets[i], offsets[i+1])
 // (offsets != NULL; a decreasing pair gives flags 0) or msg_len bytes at

@@ -1337,6 +1337,9 @@ extern "C" int hsvi_set_inject(int mode) {
   return prev;
 }
 extern "C" int hsvi_inject_mode(void) { return (int)t_inject; }
+// for the point-pass launchers of other translation units (hsv_mempool.hip)
+extern "C" int hsvi_lattice_bits(void) { return g_lat_bits.load(); }
+extern "C" uint32_t hsvi_next_nonce(void) { return next_nonce(); }
 
 namespace {
 __global__ void hsv_fault_exchange_kernel(uint32_t *words, uint32_t *out) {

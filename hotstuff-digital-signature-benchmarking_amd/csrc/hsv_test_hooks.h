@@ -90,6 +90,14 @@ HSV_API size_t hsv_test_tx_sign_chunk(size_t items);
  * several launches and its offsets are rebased.  0 restores the product's.
  * Returns the previous value. */
 HSV_API size_t hsv_test_stage_bytes(size_t bytes);
+/* Tests: how the calling thread's last hsv_committee_verify_transactions* call
+ * split its batch, summed over its rounds: out[0] transactions verified from
+ * a member's comb table (hits), out[1] by the generic kernels (misses),
+ * out[2] those of the misses that took the full-length fallback path.  The
+ * lengths live on the device: after the device form they are valid once the
+ * caller has synchronised its stream.  HSV_OK, or HSV_ERR_INVALID_ARG when the
+ * thread has made no such call. */
+HSV_API int hsv_test_committee_tx_counts(uint64_t out[3]);
 
 #ifdef __cplusplus
 }

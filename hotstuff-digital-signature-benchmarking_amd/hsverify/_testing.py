@@ -113,3 +113,12 @@ def lanesplit_check(words):
     if rc != 0:
         raise RuntimeError(f"hsv_test_lanesplit_check failed: hipError {rc}")
     return out
+
+
+def committee_tx_counts() -> tuple:
+    """(hits, misses, fallback items) of the calling thread's last
+    Committee.verify_transactions* call, summed over its rounds (test library;
+    after the device form, synchronise first)."""
+    out = (ctypes.c_uint64 * 3)()
+    _lib.check(_lib.hook("hsv_test_committee_tx_counts")(out), "hsv_test_committee_tx_counts")
+    return int(out[0]), int(out[1]), int(out[2])

@@ -77,6 +77,51 @@ class Committee:
             ctypes.c_void_p(flags.data_ptr()), _fault_ptr(fault), ctypes.c_void_p(stream))
         _lib.check(rc, "hsv_committee_verify_device")
 
+    def verify_transactions(self, txs) -> np.ndarray:
+        """Ragged list of mempool transactions (``message || pk || sig``, mempool.py)
+        -> flag bytes, bit for bit those of mempool.verify_transactions: a
+        transaction signed by a member takes the member's comb table, any other
+        the generic kernels.  Raises HsvLibraryError for a transaction shorter
+        than 96 bytes."""
+        from .mempool import pack
+        txs = list(txs)
+        out = np.zeros(len(txs), np.uint8)
+        if txs:
+            buf, offsets = pack(txs)
+            _lib.check(self._lib.hsv_committee_verify_transactions(self._h, _ptr(buf), _ptr(offsets), 0, len(txs),
+                                                                   _ptr(out)), "hsv_committee_verify_transactions")
+        return out
+
+    def verify_transactions_fixed(self, txs) -> np.ndarray:
+        """(n, tx_size) u8 array of equal-size transactions -> (n,) flag bytes."""
+        txs = np.ascontiguousarray(txs, dtype=np.uint8)
+        if txs.ndim != 2:
+            raise ValueError("expected an (n, tx_size) array")
+        n, size = txs.shape
+        out = np.zeros(n, np.uint8)
+        if n:
+            _lib.check(self._lib.hsv_committee_verify_transactions(self._h, _ptr(txs), None, size, n, _ptr(out)),
+                       "hsv_committee_verify_transactions")
+        return out
+
+    def verify_transactions_device(self, txs, offsets=None, tx_size: int = 0, n=None, flags=None, strict_bits=None,
+                                   stream=None, fault=None) -> None:
+        """Device tensors, as mempool.verify_transactions_device: txs uint8,
+        offsets int64 (n + 1) or None with tx_size; flags (n,) uint8 and / or
+        strict_bits (ceil(n / 32),) int32.  No synchronisation."""
+        from .verifier import _fault_ptr
+        import torch
+        if n is None:
+            n = offsets.numel() - 1 if offsets is not None else txs.numel() // tx_size
+        if stream is None:
+            stream = torch.cuda.current_stream(txs.device).cuda_stream
+        rc = self._lib.hsv_committee_verify_transactions_device(
+            self._h, ctypes.c_void_p(txs.data_ptr()), ctypes.c_void_p(offsets.data_ptr()) if offsets is not None else None,
+            tx_size, n, ctypes.c_void_p(flags.data_ptr()) if flags is not None else None,
+            ctypes.c_void_p(strict_bits.data_ptr()) if strict_bits is not None else None, _fault_ptr(fault),
+            ctypes.c_void_p(stream))
+        _lib.check(rc, "hsv_committee_verify_transactions_device")
+
     def close(self) -> None:
         if self._h:
             self._lib.hsv_committee_destroy(self._h)

@@ -100,17 +100,21 @@ def verify_transactions_device(txs, offsets=None, tx_size: int = 0, n: int | Non
     _lib.check(rc, "hsv_verify_transactions_device")
 
 
-def filter_transactions(txs: Sequence[bytes]) -> List[bytes]:
+def filter_transactions(txs: Sequence[bytes], committee=None) -> List[bytes]:
     """``BatchMaker::run`` with the check enabled (batch_maker.rs:79-97): the
-    transactions whose signature verifies, in order."""
-    flags = verify_transactions(txs)
+    transactions whose signature verifies, in order.  ``committee`` (a
+    committee.Committee of the known clients' keys): its members' transactions
+    are verified from their comb tables, with the same result."""
+    flags = committee.verify_transactions(txs) if committee is not None else verify_transactions(txs)
     return [t for t, f in zip(txs, flags) if f & _lib.STRICT_OK]
 
 
-def verify_batch_transactions(txs: Iterable[bytes]) -> bool:
+def verify_batch_transactions(txs: Iterable[bytes], committee=None) -> bool:
     """``Core::make_vote`` batch re-check (core.rs:121-131): True iff every
-    transaction of the batch verifies (an empty batch passes)."""
+    transaction of the batch verifies (an empty batch passes).  ``committee``
+    as in :func:`filter_transactions`."""
     txs = list(txs)
     if not txs:
         return True
-    return bool((verify_transactions(txs) & _lib.STRICT_OK).all())
+    flags = committee.verify_transactions(txs) if committee is not None else verify_transactions(txs)
+    return bool((flags & _lib.STRICT_OK).all())

@@ -12,7 +12,8 @@
  *                                                                   hsv_verify_msgs_device
  *   crypto::Signature::new           crypto/src/lib.rs:185-191  -> hsv_sign, hsv_signer_sign*
  *   crypto::generate_keypair         crypto/src/lib.rs:167-175  -> hsv_public_key, hsv_signer_create
- *   mempool transaction check  mempool/src/batch_maker.rs:79-85 -> hsv_verify_transactions*
+ *   mempool transaction check  mempool/src/batch_maker.rs:79-85 -> hsv_verify_transactions*,
+ *                                                                   hsv_committee_verify_transactions*
  *   QC / TC signature checks from wire bytes
  *                        consensus/src/messages.rs:180-198, 290-315 -> hsv_qc_verify_bincode,
  *                                                                   hsv_tc_verify_bincode
@@ -273,6 +274,42 @@ HSV_API int hsv_committee_verify_batch_packed(hsv_committee *c, const uint8_t di
 HSV_API int hsv_committee_verify_device(const hsv_committee *c, const uint32_t *d_key_idx, const uint8_t *d_sig,
                                 size_t sig_stride, const uint8_t *d_msg, size_t msg_stride, size_t m,
                                 uint8_t *d_flags, uint32_t *d_fault, void *stream);
+/* Mempool transactions (layout and scheme of hsv_verify_transactions* below)
+ * whose signers are mostly members of c.  Flags are bit for bit those of
+ * hsv_verify_transactions* for the same bytes: a transaction whose pk bytes
+ * equal a member's takes that member's comb table, any other the generic
+ * kernels; which it is, is decided on the device, per transaction.  An empty
+ * committee is valid (everything takes the generic kernels).
+ * offsets != NULL: a ragged batch, n + 1 entries relative to txs; offsets ==
+ * NULL: fixed tx_size.  txs at any alignment.
+ * Host form: synchronous, on the committee's device, one staged copy per
+ * launch (neither pipelined nor sharded across devices: the tables live on
+ * one).  A transaction shorter than 96 bytes, or decreasing offsets, is
+ * HSV_ERR_INVALID_ARG before any device work; a failed device self-check is
+ * HSV_ERR_DEVICE_FAULT.
+ * Device form: stream-ordered, never synchronises; device = the committee's
+ * (as hsv_committee_verify_device).  d_flags / d_strict_bits: either may be
+ * NULL, not both; every flag byte and strict word of the n transactions is
+ * written.  A transaction shorter than 96 bytes, or whose offsets decrease,
+ * gets flags 0 and strict bit 0 (its neighbours are unaffected); tx_size < 96
+ * with d_offsets == NULL is HSV_ERR_INVALID_ARG.  d_fault (optional) as
+ * hsv_verify_device_bits: word 0 from the curve self-check of either route,
+ * word 1 from the generic route's canaries.  Batches above 2^22 run as rounds
+ * of 2^22 in order on `stream`, three launches each.
+ * When to use it (profiles/committee_tx_bench_2p20.json: 2^20 device-resident
+ * transactions of 512 B, K = 4, 100 and 1000 keys, against
+ * hsv_verify_transactions_device on the same bytes in the same run): with
+ * every signer a member the call takes 0.40 of that call's time at each K
+ * (2.49 - 2.52 x the rate); with half of the transactions members', 0.72 -
+ * 0.73; with no member at all, 1.00 (0.995 - 1.004): the lookup costs
+ * nothing measurable, and a caller who knows few of its signers loses
+ * nothing but the committee's table memory (384 KiB per key). */
+HSV_API int hsv_committee_verify_transactions(hsv_committee *c, const uint8_t *txs, const uint64_t *offsets,
+                                              size_t tx_size, size_t n, uint8_t *flags_out);
+HSV_API int hsv_committee_verify_transactions_device(const hsv_committee *c, const uint8_t *d_txs,
+                                                     const uint64_t *d_offsets, size_t tx_size, size_t n,
+                                                     uint8_t *d_flags, uint32_t *d_strict_bits,
+                                                     uint32_t *d_fault, void *stream);
 
 /* ---- mempool transactions -------------------------- */
 /* A client transaction is  message || pk (32 B) || sig (64 B, R||s)  and its
