@@ -635,8 +635,8 @@ int device_fault_words(DevCtx &c, uint32_t **out) {
   std::lock_guard<std::mutex> lk(c.table_mu);
   if (!c.d_fault) {
     uint32_t *p = nullptr;
-    hipError_t e = hipMalloc(&p, 256);
-    if (e == hipSuccess) e = hipMemset(p, 0, 256);
+    hipError_t e = hipMalloc(&p, kDeviceFaultBytes);
+    if (e == hipSuccess) e = hipMemset(p, 0, kDeviceFaultBytes);
     if (e != hipSuccess) {
       if (p) {
         ResidentPause pause;

@@ -235,4 +235,53 @@ HSV_INL uint32_t verify_one_comb(const uint32_t pk[8], uint32_t key_flags, const
          (a_ok ? kAOk : 0u) | (r_ok ? kROk : 0u) | fault_bit(a_ok, r_ok, q);
 }
 
+// The same after the hash: k = SHA-512(R || A || M) mod l, whatever the length
+// of M (the committee message path reads it from the route kernel's record,
+// hsv_committee_msgs.hip), so no key bytes are needed.  verify_one_comb's body
+// from the recoding on, kept as a function of its own: with verify_one_comb
+// written as the hash plus a call of this one, hipcc compiled
+// hsv_comb_verify_kernel and hsv_ctx_comb_kernel to two and three instructions
+// more than before.  tests/native/comb_k_host.cpp holds the two
+// to the same byte.
+HSV_INL uint32_t verify_one_comb_k(uint32_t key_flags, const uint32_t sig[16], const sc &k, const uint32_t *ta,
+                                   const uint32_t *tb, uint32_t inject = kInjectNone) {
+  const uint32_t s_ok = sc_is_canonical(sig + 8);
+  uint32_t kr[9], sr[9];
+  recode_add<9, 8, kCombPos>(k.v, 8, kr);
+  recode_add<9, 8, kCombPos>(sig + 8, 8, sr);
+
+  ge_ext q = ge_identity();
+  HSV_NOUNROLL
+  for (int j = 0; j < kCombPos; ++j) {
+    const uint32_t ca = kr[0] & 0xffu, cb = sr[0] & 0xffu;
+    HSV_UNROLL
+    for (int i = 0; i < 8; ++i) {
+      kr[i] = (kr[i] >> 8) | (kr[i + 1] << 24);
+      sr[i] = (sr[i] >> 8) | (sr[i + 1] << 24);
+    }
+    kr[8] >>= 8;
+    sr[8] >>= 8;
+    const CombPosTab tpa{ta + (uint64_t)j * kCombEnt * kCombEntryWords};
+    const CombPosTab tpb{tb + (uint64_t)j * kCombEnt * kCombEntryWords};
+    ge_niels na = select_niels<8>(tpa, ca);
+    if (inject != kInjectNone && j == 0) na = niels_injected(na, inject);
+    q = ge_add_niels<true>(q, na);
+    q = ge_add_niels<true>(q, select_niels<8>(tpb, cb));
+  }
+
+  fe rx, ry;
+  const uint32_t r_ok = ge_decompress(sig, rx, ry);
+  const uint32_t small_r = r_ok & y_is_small_order(ry);
+  const uint32_t same = ge_eq_affine(q, rx, ry);
+  const uint32_t a_ok = (key_flags & kKeyAOk) ? 1u : 0u;
+  const uint32_t small_a = a_ok & ((key_flags & kKeySmallA) ? 1u : 0u);
+
+  const uint32_t parse_ok = s_ok & a_ok & r_ok;
+  const uint32_t eq_ok = parse_ok & same;
+  const uint32_t strict_ok = eq_ok & (small_a ^ 1u) & (small_r ^ 1u);
+  return (strict_ok ? kStrictOk : 0u) | (eq_ok ? kEqOk : 0u) | (parse_ok ? kParseOk : 0u) |
+         (small_a ? kSmallA : 0u) | (small_r ? kSmallR : 0u) | (s_ok ? kSOk : 0u) |
+         (a_ok ? kAOk : 0u) | (r_ok ? kROk : 0u) | fault_bit(a_ok, r_ok, q);
+}
+
 }  // namespace hsv

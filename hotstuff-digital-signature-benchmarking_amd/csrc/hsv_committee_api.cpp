@@ -759,21 +759,41 @@ struct TxCountRef {
   unsigned slot = 0;
 };
 thread_local TxCountRef t_tx_counts;
+thread_local TxCountRef t_msg_counts;  // the same of the message calls (committee_msgs_counts)
 
-// Takes the next slot of device c (current) for this call and zeroes it on
+// Takes the next slot (of those at byte `off` of the device's self-check
+// block, dealt by `rr`) of device c (current) for this call and zeroes it on
 // `stream`; out: the slot's three 64-bit words.
-int tx_counts_begin(DevCtx &c, hipStream_t stream, uint64_t **out) {
+int counts_begin(DevCtx &c, hipStream_t stream, size_t off, std::atomic<unsigned> &rr, TxCountRef &ref,
+                 uint64_t **out) {
   uint32_t *words = nullptr;
   const int rc = device_fault_words(c, &words);
   if (rc != HSV_OK) return rc;
-  const unsigned slot = c.tx_count_rr.fetch_add(1) % kTxCountSlots;
-  uint8_t *p = reinterpret_cast<uint8_t *>(words) + kTxCountOff + slot * kTxCountBytes;
+  const unsigned slot = rr.fetch_add(1) % kTxCountSlots;
+  uint8_t *p = reinterpret_cast<uint8_t *>(words) + off + slot * kTxCountBytes;
   const hipError_t e = hipMemsetAsync(p, 0, kTxCountBytes, stream);
   if (e != hipSuccess) return hip_fail("zeroing the call's list lengths", e);
-  t_tx_counts.device = c.device;
-  t_tx_counts.slot = slot;
+  ref.device = c.device;
+  ref.slot = slot;
   *out = reinterpret_cast<uint64_t *>(p);
   return HSV_OK;
+}
+int tx_counts_begin(DevCtx &c, hipStream_t stream, uint64_t **out) {
+  return counts_begin(c, stream, kTxCountOff, c.tx_count_rr, t_tx_counts, out);
+}
+
+// the three words of the slot `ref` names
+int counts_read(const TxCountRef &ref, size_t off, const char *none, uint64_t out[3]) {
+  if (!out) return fail(HSV_ERR_INVALID_ARG, "null argument");
+  if (ref.device < 0) return fail(HSV_ERR_INVALID_ARG, none);
+  DevCtx &c = ctx(ref.device);
+  DeviceGuard guard(c.device);
+  uint32_t *words = nullptr;
+  const int rc = device_fault_words(c, &words);
+  if (rc != HSV_OK) return rc;
+  const hipError_t e = hipMemcpy(out, reinterpret_cast<uint8_t *>(words) + off + ref.slot * kTxCountBytes,
+                                 3 * sizeof(uint64_t), hipMemcpyDeviceToHost);
+  return e == hipSuccess ? HSV_OK : hip_fail("hipMemcpy", e);
 }
 
 // n transactions already in HBM, in rounds of kChunk in order on `stream`
@@ -860,19 +880,90 @@ int committee_tx_host(const hsv_committee &cm, const uint8_t *txs, const uint64_
   return HSV_OK;
 }
 
+// ---- whole messages of known signers ---------------------------------------------------
+// hsv_committee_verify_msgs*: the message addressing and scheme of
+// hsv_verify_msgs* (hsv_msgs_api.cpp), routed per item on the device as the
+// transaction calls above -- three launches per round of at most kChunk items
+// (hsv_launch_committee_msgs, hsv_committee_msgs.hip), no host round trip.
+
+// n items already in HBM, in rounds of kChunk in order on `s` (d_offsets
+// relative to d_msgs, so a round only moves along the offsets)
+int committee_msgs_enqueue(const hsv_committee &cm, const uint32_t *btable, const uint32_t *comb16, const uint8_t *d_pk,
+                           size_t pk_stride, const uint8_t *d_sig, size_t sig_stride, const uint8_t *d_msgs,
+                           const uint64_t *d_offsets, size_t msg_len, size_t msg_stride, size_t n, uint8_t *d_flags,
+                           uint32_t *d_bits, uint32_t *d_fault, uint64_t *d_totals, hipStream_t s) {
+  for (size_t base = 0; base < n; base += kChunk) {
+    const size_t m = std::min(kChunk, n - base);
+    const hipError_t e = hsv_launch_committee_msgs(
+        d_pk + base * pk_stride, pk_stride, d_sig + base * sig_stride, sig_stride,
+        d_offsets ? d_msgs : d_msgs + base * msg_stride, d_offsets ? d_offsets + base : nullptr, msg_len, msg_stride,
+        (uint32_t)m, cm.d_keytab, cm.keymask, KeyHash::seed(), cm.dev.d_pks, cm.dev.d_kflags, cm.dev.n,
+        cm.dev.d_tabptr, btable, comb16, d_flags ? d_flags + base : nullptr, d_bits ? d_bits + base / 32 : nullptr,
+        d_fault, d_totals, s);
+    if (e != hipSuccess) return hip_fail("committee message launch", e);
+  }
+  return HSV_OK;
+}
+
+// The host form: plain staged copies on the committee's device, chunked as
+// hsv_verify_msgs (at most kChunk items and the staging cap of message bytes
+// per round); neither pipelined nor sharded, the tables live on one device.
+int committee_msgs_host(const hsv_committee &cm, const uint8_t *pk, const uint8_t *sig, const uint8_t *msgs,
+                        const uint64_t *offsets, size_t msg_len, size_t msg_stride, size_t n, uint8_t *flags_out) {
+  DevCtx &c = ctx(cm.dev.device);
+  DeviceGuard guard(c.device);
+  if (guard.status() != hipSuccess) return hip_fail("hipSetDevice", guard.status());
+  int rc = ensure_btable(c);
+  if (rc == HSV_OK) rc = ensure_btable16(c);
+  if (rc != HSV_OK) return rc;
+  SlotLease lease(c);
+  Slot &slot = lease.slot();
+  rc = slot_prepare(slot, 0, 0);
+  if (rc != HSV_OK) return rc;
+  hipStream_t st = slot.stream;
+  uint64_t *d_totals = nullptr;
+  rc = counts_begin(c, st, kMsgCountOff, c.msg_count_rr, t_msg_counts, &d_totals);
+  if (rc != HSV_OK) return rc;
+  const BatchSpan span{offsets, msg_stride, msg_len};
+  std::vector<uint64_t> rel;  // a chunk's offsets, relative to its first byte
+  for (size_t a = 0, b; a < n; a = b) {
+    b = span.chunk_end(a, n, kChunk, g_stage_bytes.load());
+    const size_t m = b - a, bytes = span.span_bytes(a, b);
+    StagedBlock blk(st);
+    const size_t off_flags = blk.add(m), off_pk = blk.add(m * 32), off_sig = blk.add(m * 64);
+    const size_t off_offs = blk.add(offsets ? (m + 1) * 8 : 0), off_msg = blk.add(bytes);
+    // unwritten flags read as rejections
+    rc = blk.alloc("allocating the committee message buffers", m);
+    if (rc != HSV_OK) return rc;
+    blk.in(off_pk, pk + a * 32, m * 32);
+    blk.in(off_sig, sig + a * 64, m * 64);
+    if (offsets) {
+      rel.resize(m + 1);
+      span.rel_offsets(a, b, rel.data());
+      blk.in(off_offs, rel.data(), (m + 1) * 8);
+    }
+    blk.in(off_msg, msgs + span.first_byte(a), bytes);
+    if (blk.ok())
+      blk.step(hsv_launch_committee_msgs(
+          blk.at(off_pk), 32, blk.at(off_sig), 64, blk.at(off_msg),
+          offsets ? reinterpret_cast<uint64_t *>(blk.at(off_offs)) : nullptr, msg_len, msg_stride, (uint32_t)m,
+          cm.d_keytab, cm.keymask, KeyHash::seed(), cm.dev.d_pks, cm.dev.d_kflags, cm.dev.n, cm.dev.d_tabptr,
+          c.d_btable, c.d_btable16, blk.at(off_flags), nullptr, blk.fault(), d_totals, st));
+    blk.out(flags_out + a, off_flags, m);
+    rc = blk.finish("hsv_committee_verify_msgs");
+    if (rc != HSV_OK) return rc;
+  }
+  return HSV_OK;
+}
+
 }  // namespace
 
 int committee_tx_counts(uint64_t out[3]) {
-  if (!out) return fail(HSV_ERR_INVALID_ARG, "null argument");
-  if (t_tx_counts.device < 0) return fail(HSV_ERR_INVALID_ARG, "no committee transaction call on this thread");
-  DevCtx &c = ctx(t_tx_counts.device);
-  DeviceGuard guard(c.device);
-  uint32_t *words = nullptr;
-  const int rc = device_fault_words(c, &words);
-  if (rc != HSV_OK) return rc;
-  const hipError_t e = hipMemcpy(out, reinterpret_cast<uint8_t *>(words) + kTxCountOff + t_tx_counts.slot * kTxCountBytes,
-                                 3 * sizeof(uint64_t), hipMemcpyDeviceToHost);
-  return e == hipSuccess ? HSV_OK : hip_fail("hipMemcpy", e);
+  return counts_read(t_tx_counts, kTxCountOff, "no committee transaction call on this thread", out);
+}
+
+int committee_msgs_counts(uint64_t out[3]) {
+  return counts_read(t_msg_counts, kMsgCountOff, "no committee message call on this thread", out);
 }
 
 }  // namespace hsvh
@@ -906,6 +997,53 @@ int hsv_committee_verify_transactions_device(const hsv_committee *cm, const uint
   if (rc != HSV_OK) return rc;
   return committee_tx_enqueue(*cm, call.comb, call.comb16, d_txs, d_offsets, tx_size, n, d_flags, d_strict_bits,
                               call.fault, d_totals, call.stream);
+}
+
+int hsv_committee_verify_msgs(hsv_committee *cm, const uint8_t *pk, const uint8_t *sig, const uint8_t *msgs,
+                              const uint64_t *offsets, size_t msg_len, size_t msg_stride, size_t n,
+                              uint8_t *flags_out) {
+  CallScope call;
+  if (n == 0) return HSV_OK;
+  if (!cm || !pk || !sig || !flags_out) return fail(HSV_ERR_INVALID_ARG, "null argument");
+  if (n > 0xffffffffu) return fail(HSV_ERR_INVALID_ARG, "batch too large");
+  bool any_bytes = msg_len != 0;
+  if (offsets) {
+    const size_t bad = first_bad_item(offsets, n, 0);
+    if (bad != n) return fail(HSV_ERR_INVALID_ARG, "offsets decrease at message " + std::to_string(bad));
+    any_bytes = offsets[n] != offsets[0];
+  } else if (msg_stride != 0 && msg_stride < msg_len) {
+    return fail(HSV_ERR_INVALID_ARG, "messages overlap");
+  }
+  if (any_bytes && !msgs) return fail(HSV_ERR_INVALID_ARG, "null msgs");
+  const int rc = ensure_init();  // before the handle is read: without a device there is no committee
+  if (rc != HSV_OK) return rc;
+  return committee_msgs_host(*cm, pk, sig, msgs, offsets, msg_len, msg_stride, n, flags_out);
+}
+
+int hsv_committee_verify_msgs_device(const hsv_committee *cm, const uint8_t *d_pk, size_t pk_stride,
+                                     const uint8_t *d_sig, size_t sig_stride, const uint8_t *d_msgs,
+                                     const uint64_t *d_offsets, size_t msg_len, size_t msg_stride, size_t n,
+                                     uint8_t *d_flags, uint32_t *d_strict_bits, uint32_t *d_fault, void *stream) {
+  if (n == 0) return HSV_OK;
+  if (!cm || !d_pk || !d_sig) return fail(HSV_ERR_INVALID_ARG, "null argument");
+  if (!d_msgs && (d_offsets || msg_len)) return fail(HSV_ERR_INVALID_ARG, "null d_msgs");
+  if (!d_flags && !d_strict_bits) return fail(HSV_ERR_INVALID_ARG, "no output");
+  const uintptr_t mis =
+      (reinterpret_cast<uintptr_t>(d_pk) | reinterpret_cast<uintptr_t>(d_sig) | pk_stride | sig_stride) & 15u;
+  if (mis) return fail(HSV_ERR_ALIGN, "d_pk, d_sig and their strides must be multiples of 16");
+  if (reinterpret_cast<uintptr_t>(d_offsets) & 7u) return fail(HSV_ERR_ALIGN, "d_offsets must be 8-byte aligned");
+  if (pk_stride < 32 || sig_stride < 64) return fail(HSV_ERR_INVALID_ARG, "record strides overlap");
+  if (!d_offsets && msg_stride != 0 && msg_stride < msg_len) return fail(HSV_ERR_INVALID_ARG, "messages overlap");
+  int rc = ensure_init();  // before the handle is read: without a device there is no committee
+  if (rc != HSV_OK) return rc;
+  DeviceCall call;
+  rc = call.begin(d_pk, stream, d_fault, DeviceCall::kBoth, "committee", cm->dev.device);
+  if (rc != HSV_OK) return rc;
+  uint64_t *d_totals = nullptr;
+  rc = counts_begin(*call.c, call.stream, kMsgCountOff, call.c->msg_count_rr, t_msg_counts, &d_totals);
+  if (rc != HSV_OK) return rc;
+  return committee_msgs_enqueue(*cm, call.comb, call.comb16, d_pk, pk_stride, d_sig, sig_stride, d_msgs, d_offsets,
+                                msg_len, msg_stride, n, d_flags, d_strict_bits, call.fault, d_totals, call.stream);
 }
 
 }  // extern "C"

@@ -137,6 +137,7 @@ struct DevCtx {
   std::vector<hipStream_t> side_free;    // idle second streams of multi-chunk device-API batches
   std::vector<hipStream_t> side_all;     // every side stream created (hsv_shutdown)
   std::atomic<unsigned> tx_count_rr{0};  // next list-length slot of d_fault (committee_tx_counts)
+  std::atomic<unsigned> msg_count_rr{0};  // the same of the message calls (committee_msgs_counts)
 };
 
 // Makes `device` current for the calling thread and restores the previous
@@ -197,6 +198,10 @@ constexpr size_t kFaultOutWord = 4;  // d_fault[4..5]: output of hsv_launch_faul
 // lengths of the committee transaction calls (committee_tx_counts); a call
 // takes the next slot in turn
 constexpr size_t kTxCountSlots = 6, kTxCountOff = 64, kTxCountBytes = 32;
+// d_fault bytes [256, 448): the same for the committee message calls
+// (committee_msgs_counts), slots of their own
+constexpr size_t kMsgCountOff = 256;
+constexpr size_t kDeviceFaultBytes = 512;  // the whole block
 // The words a device-API call reports into: the caller's d_fault (zeroed on
 // `stream` here), or the per-device words when d_fault is NULL.
 int call_fault_words(DevCtx &c, uint32_t *d_fault, hipStream_t stream, uint32_t **out);
@@ -344,6 +349,8 @@ int resident_set_mode(int on);      // hsv_set_resident_service
 // test hook (hsv_test_committee_tx_counts): hits, misses and fallback items of
 // the calling thread's last hsv_committee_verify_transactions* call
 int committee_tx_counts(uint64_t out[3]);
+// the same of its last hsv_committee_verify_msgs* call (hsv_test_committee_msgs_counts)
+int committee_msgs_counts(uint64_t out[3]);
 
 // The generic host-buffer path (hsv_capi.cpp): records at the given strides.
 int run_host(const uint8_t *pk, size_t pk_stride, const uint8_t *sig, size_t sig_stride, const uint8_t *msg,

@@ -244,6 +244,21 @@ hipError_t hsv_launch_msg_prep(const uint8_t *pk, uint64_t pk_stride, const uint
                                const uint8_t *msgs, const uint64_t *offsets, uint64_t msg_len, uint64_t msg_stride,
                                uint32_t n, uint32_t *prep, uint32_t *fb_count, uint32_t *fb_list, int lat_bits,
                                hipStream_t stream);
+// One round (n <= 2^22) of hsv_committee_verify_msgs* (hsv_committee_msgs.hip):
+// the messages of hsv_launch_verify_msgs with the committee arguments of
+// hsv_launch_committee_tx.  Three launches on `stream`: the route kernel (the
+// message hash, the key lookup, hit and miss lists, k mod l for the hits, the
+// misses' prepass), the comb pass over the hit list and the generic pass over
+// the miss list; both read pk / sig in place and never a message byte.  Every
+// flag byte and strict word of the round is written (a decreasing pair of
+// offsets: flags 0); fault, totals and nkeys == 0 as hsv_launch_committee_tx.
+hipError_t hsv_launch_committee_msgs(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, uint64_t sig_stride,
+                                     const uint8_t *msgs, const uint64_t *offsets, uint64_t msg_len,
+                                     uint64_t msg_stride, uint32_t n, const uint32_t *keytab, uint32_t keymask,
+                                     uint64_t seed, const uint8_t *pks, const uint8_t *key_flags, uint32_t nkeys,
+                                     const uint32_t *const *key_tables, const uint32_t *btable,
+                                     const uint32_t *comb16, uint8_t *flags_out, uint32_t *strict_bits,
+                                     uint32_t *fault, uint64_t *totals, hipStream_t stream);
 // flags 0 (and STRICT_OK bit cleared) for transactions shorter than 96 bytes
 hipError_t hsv_launch_tx_mask(const uint64_t *offsets, uint32_t n, uint8_t *flags, uint32_t *strict_bits,
                               hipStream_t stream);

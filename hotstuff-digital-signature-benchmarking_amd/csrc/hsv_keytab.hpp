@@ -1,5 +1,7 @@
 // Member index by key, on the device: the lookup of the committee
-// transaction path (hsv_committee_verify_transactions*, hsv_mempool.hip).
+// transaction path (hsv_committee_verify_transactions*, hsv_mempool.hip) and
+// of the committee message path (hsv_committee_verify_msgs*,
+// hsv_committee_msgs.hip).
 //
 // A transaction carries its signer's 32 raw key bytes; whether they are a
 // committee member's decides which kernels verify it.  The table is the

@@ -98,6 +98,10 @@ HSV_API size_t hsv_test_stage_bytes(size_t bytes);
  * caller has synchronised its stream.  HSV_OK, or HSV_ERR_INVALID_ARG when the
  * thread has made no such call. */
 HSV_API int hsv_test_committee_tx_counts(uint64_t out[3]);
+/* Tests: the same for the calling thread's last hsv_committee_verify_msgs*
+ * call (items instead of transactions).  The two hooks keep slots of their
+ * own: a call of one kind leaves the other hook's answer as it was. */
+HSV_API int hsv_test_committee_msgs_counts(uint64_t out[3]);
 
 #ifdef __cplusplus
 }

@@ -122,3 +122,12 @@ def committee_tx_counts() -> tuple:
     out = (ctypes.c_uint64 * 3)()
     _lib.check(_lib.hook("hsv_test_committee_tx_counts")(out), "hsv_test_committee_tx_counts")
     return int(out[0]), int(out[1]), int(out[2])
+
+
+def committee_msgs_counts() -> tuple:
+    """(hits, misses, fallback items) of the calling thread's last
+    Committee.verify_msgs* call, summed over its rounds (test library; after
+    the device form, synchronise first)."""
+    out = (ctypes.c_uint64 * 3)()
+    _lib.check(_lib.hook("hsv_test_committee_msgs_counts")(out), "hsv_test_committee_msgs_counts")
+    return int(out[0]), int(out[1]), int(out[2])

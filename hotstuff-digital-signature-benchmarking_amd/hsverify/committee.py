@@ -122,6 +122,58 @@ class Committee:
             ctypes.c_void_p(stream))
         _lib.check(rc, "hsv_committee_verify_transactions_device")
 
+    def verify_msgs(self, pk, sig, msgs) -> np.ndarray:
+        """Whole messages of any length, as verifier.verify_msgs (pk (n,32),
+        sig (n,64), ``msgs`` a sequence of n ``bytes`` or a ``(buffer,
+        offsets)`` pair) -> flag bytes, bit for bit that call's: an item signed
+        by a member takes the member's comb table, any other the generic
+        kernels.  Decreasing offsets raise HsvLibraryError."""
+        from .verifier import pack_msgs
+        pk = np.ascontiguousarray(pk, dtype=np.uint8).reshape(-1, 32)
+        sig = np.ascontiguousarray(sig, dtype=np.uint8).reshape(-1, 64)
+        n = pk.shape[0]
+        if sig.shape[0] != n:
+            raise ValueError("pk/sig length mismatch")
+        if isinstance(msgs, tuple) and len(msgs) == 2 and not isinstance(msgs[0], (bytes, bytearray, memoryview)):
+            buf = np.ascontiguousarray(msgs[0], dtype=np.uint8).reshape(-1)
+            offsets = np.ascontiguousarray(msgs[1], dtype=np.uint64).reshape(-1)
+        else:
+            buf, offsets = pack_msgs(msgs)
+        if offsets.size != n + 1:
+            raise ValueError("one message per item (n + 1 offsets)")
+        if n and buf.size < int(offsets.max()):
+            raise ValueError("offsets run past the buffer")
+        out = np.zeros(n, dtype=np.uint8)
+        if n:
+            _lib.check(self._lib.hsv_committee_verify_msgs(self._h, _ptr(pk), _ptr(sig), _ptr(buf) if buf.size else None,
+                                                           _ptr(offsets), 0, 0, n, _ptr(out)),
+                       "hsv_committee_verify_msgs")
+        return out
+
+    def verify_msgs_device(self, pk, sig, msgs, offsets=None, msg_len: int = 0, msg_stride: int | None = None,
+                           flags=None, strict_bits=None, stream=None, fault=None) -> None:
+        """Device tensors, as verifier.verify_msgs_device: pk (n,32) and sig
+        (n,64) rows at strides that are multiples of 16, ``msgs`` at any
+        alignment, ``offsets`` int64 (n + 1) or None for ``msg_len`` bytes per
+        item at ``msg_stride`` (default msg_len; 0 = one shared message);
+        ``flags`` (n,) uint8 and / or ``strict_bits`` (ceil(n / 32),) int32.
+        No synchronisation."""
+        from .verifier import _fault_ptr
+        import torch
+        n = pk.shape[0]
+        for t in (sig, msgs, offsets, flags, strict_bits, fault):
+            if t is not None and t.device != pk.device:
+                raise ValueError(f"all tensors must live on {pk.device}, got {t.device}")
+        if msg_stride is None:
+            msg_stride = msg_len
+        if stream is None:
+            stream = torch.cuda.current_stream(pk.device).cuda_stream
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        rc = self._lib.hsv_committee_verify_msgs_device(
+            self._h, p(pk), pk.stride(0), p(sig), sig.stride(0), p(msgs), p(offsets), msg_len, msg_stride, n,
+            p(flags), p(strict_bits), _fault_ptr(fault), ctypes.c_void_p(stream))
+        _lib.check(rc, "hsv_committee_verify_msgs_device")
+
     def close(self) -> None:
         if self._h:
             self._lib.hsv_committee_destroy(self._h)

@@ -9,7 +9,8 @@
  *                                                                   hsv_verify_batch_packed
  *   (batched strict API)                     -> hsv_verify
  *   (the same over whole messages of any length, RFC 8032 5.1.7) -> hsv_verify_msgs,
- *                                                                   hsv_verify_msgs_device
+ *                                                                   hsv_verify_msgs_device,
+ *                                                                   hsv_committee_verify_msgs*
  *   crypto::Signature::new           crypto/src/lib.rs:185-191  -> hsv_sign, hsv_signer_sign*
  *   crypto::generate_keypair         crypto/src/lib.rs:167-175  -> hsv_public_key, hsv_signer_create
  *   mempool transaction check  mempool/src/batch_maker.rs:79-85 -> hsv_verify_transactions*,
@@ -107,7 +108,9 @@ HSV_API const char *hsv_last_error(void);
  * three device-API calls (hsv_verify_device_bits, hsv_committee_verify_device,
  * hsv_verify_transactions_device) take the optional d_fault argument before
  * `stream`; a caller built against 0.2.x headers must be rebuilt (check
- * HSV_ABI_VERSION against hsv_abi_version() at startup). */
+ * HSV_ABI_VERSION against hsv_abi_version() at startup).  Entry points added
+ * since (the last: hsv_committee_verify_msgs*) change no existing signature
+ * and leave both the version and HSV_ABI_VERSION as they are. */
 #define HSV_ABI_VERSION 3
 HSV_API const char *hsv_version(void);
 /* The ABI generation this library implements (HSV_ABI_VERSION of its header). */
@@ -310,6 +313,47 @@ HSV_API int hsv_committee_verify_transactions_device(const hsv_committee *c, con
                                                      const uint64_t *d_offsets, size_t tx_size, size_t n,
                                                      uint8_t *d_flags, uint32_t *d_strict_bits,
                                                      uint32_t *d_fault, void *stream);
+/* Whole messages of any length (RFC 8032 5.1.7 PureEdDSA; addressing and
+ * scheme of hsv_verify_msgs* above) whose signers are mostly members of c.
+ * Flags are bit for bit those of hsv_verify_msgs* for the same bytes: an item
+ * whose 32 pk bytes equal a member's takes that member's comb table, any other
+ * the generic kernels; which it is, is decided on the device, per item.  An
+ * empty committee is valid; of a key listed twice the first index is used;
+ * an undecodable or small-order member key shows in HSV_A_OK / HSV_SMALL_A as
+ * everywhere else.
+ * offsets != NULL: n + 1 entries relative to msgs; offsets == NULL: msg_len
+ * bytes per item at msg_stride (0 = one shared message).  Empty messages are
+ * allowed, msgs may sit at any alignment; pk / sig pointers and strides of the
+ * device form are multiples of 16 (HSV_ERR_ALIGN).
+ * Host form: synchronous, on the committee's device, plain staged copies
+ * chunked as hsv_verify_msgs (at most 2^22 items and 2^29 message bytes per
+ * round), neither pipelined nor sharded across devices.  Decreasing offsets
+ * are HSV_ERR_INVALID_ARG before any device work; a failed device self-check
+ * is HSV_ERR_DEVICE_FAULT; without a GPU, HSV_ERR_NO_DEVICE.
+ * Device form: stream-ordered, never synchronises; device = the committee's
+ * (as hsv_committee_verify_device).  d_flags / d_strict_bits: either may be
+ * NULL, not both; every flag byte and strict word of the n items is written.
+ * An item whose offsets decrease gets flags 0 and strict bit 0 (its neighbours
+ * are unaffected).  d_fault (optional) as hsv_verify_device_bits: word 0 from
+ * the curve self-check of either route, word 1 from the generic route's
+ * canaries.  Batches above 2^22 run as rounds of 2^22 in order on `stream`,
+ * three launches each; no pass after the first reads a message byte.
+ * When to use it (profiles/committee_msgs_bench_2p20.json: 2^20 device-resident
+ * items, K = 4, 100 and 1000 keys, against hsv_verify_msgs_device on the same
+ * bytes in the same run): with every signer a member the call runs at 2.59 -
+ * 2.72 x that call's rate on 32-byte messages, 2.52 - 2.57 x on 416-byte ones
+ * and 2.32 - 2.34 x on ragged lengths 0 .. 1024; with half of the keys members
+ * it takes 0.73 - 0.77 of that call's time; with no member at all, 1.00 - 1.03:
+ * a caller who knows few of its signers loses a few percent and the
+ * committee's table memory (384 KiB per key). */
+HSV_API int hsv_committee_verify_msgs(hsv_committee *c, const uint8_t *pk, const uint8_t *sig,
+                                      const uint8_t *msgs, const uint64_t *offsets, size_t msg_len,
+                                      size_t msg_stride, size_t n, uint8_t *flags_out);
+HSV_API int hsv_committee_verify_msgs_device(const hsv_committee *c, const uint8_t *d_pk, size_t pk_stride,
+                                             const uint8_t *d_sig, size_t sig_stride, const uint8_t *d_msgs,
+                                             const uint64_t *d_offsets, size_t msg_len, size_t msg_stride,
+                                             size_t n, uint8_t *d_flags, uint32_t *d_strict_bits,
+                                             uint32_t *d_fault, void *stream);
 
 /* ---- mempool transactions -------------------------- */
 /* A client transaction is  message || pk (32 B) || sig (64 B, R||s)  and its
