@@ -231,7 +231,10 @@ hipError_t hsv_launch_committee_tx(const uint8_t *txs, const uint64_t *offsets, 
 // || M) over the whole message.  Message i is msgs[offsets[i], offsets[i+1])
 // (offsets != NULL; a decreasing pair gives flags 0) or msg_len bytes at
 // msgs + i * msg_stride; msgs at any alignment, pk / sig and their strides
-// multiples of 16.  Two launches on `stream`: hsv_launch_msg_prep
+// multiples of 16.  At <= 2^13 items one launch on `stream`: the message
+// instantiation of the small form of that size (quad, joint, row or pair, as
+// hsv_launch_verify), whose prepass wave hashes the block's messages.  Above,
+// two launches: hsv_launch_msg_prep
 // (hsv_msgs.hip: one lane per item hashes its message and writes the SoA
 // prepass record, with k mod l in the b words of a fallback item), then the
 // point pass, which never reads a message.  comb16: the wide comb of B;
@@ -240,6 +243,13 @@ hipError_t hsv_launch_verify_msgs(const uint8_t *pk, uint64_t pk_stride, const u
                                   const uint8_t *msgs, const uint64_t *offsets, uint64_t msg_len,
                                   uint64_t msg_stride, uint32_t n, uint8_t *flags_out, uint32_t *strict_bits,
                                   const uint32_t *comb16, uint32_t *fault, hipStream_t stream);
+// The route of hsv_launch_verify_msgs at <= 2^13 items (hsv_test_msgs_small):
+// -1 a small form chosen by n (default), 0 two launches as above 2^13 items,
+// 1..4 quad, joint, row, pair at every such n.  Returns the
+// previous mode, or -2 for an unknown one.  hsvi_msgs_form_counts: launches so
+// far by form -- two-launch, quad, joint, row, pair.  Neither needs a device.
+int hsvi_set_msgs_small(int mode);
+int hsvi_msgs_form_counts(uint64_t out[5]);
 hipError_t hsv_launch_msg_prep(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, uint64_t sig_stride,
                                const uint8_t *msgs, const uint64_t *offsets, uint64_t msg_len, uint64_t msg_stride,
                                uint32_t n, uint32_t *prep, uint32_t *fb_count, uint32_t *fb_list, int lat_bits,

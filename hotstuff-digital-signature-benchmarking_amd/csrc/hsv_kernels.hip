@@ -21,6 +21,7 @@
 #include "hsv_verify_hc.hpp"
 #include "hsv_rowpoint.hpp"
 #include "hsv_pointpass.hpp"
+#include "hsv_msgwave.hpp"
 
 namespace hsv {
 
@@ -308,6 +309,81 @@ hsv_verify_pair_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const
   }
 }
 
+// ---- the one-launch latency forms below, and their message instantiations ---
+// Each of the four kernels below exists twice.  MSG = false (the default, the
+// 32-byte-digest path): the prepass role hashes R || A || the 32 bytes at
+// msg + i * msg_stride.  MSG = true (messages of any length,
+// hsv_launch_verify_msgs at <= kPairMax items): the kernel takes a MsgRange in
+// place of msg, its prepass role hashes each item's whole message
+// (small_msg_prepass) and the point roles never read a message byte: a
+// fallback item's k mod l comes from the b words of its LDS record
+// (small_msg_fallback), and an item the prepass marked kPrepVoid (a decreasing
+// pair of offsets) gets flags 0, no strict bit, and no share of the helper
+// waves' work.  Everything else -- canaries, injection, self-checks, stores --
+// is one code for both.
+struct MsgRange {
+  const uint8_t *msgs;
+  const uint64_t *offsets;  // n + 1 of them, or null: msg_len bytes at msgs + i * msg_stride
+  uint64_t msg_len;
+};
+template <bool MSG>
+using SmallMsgArg = std::conditional_t<MSG, MsgRange, const uint8_t *__restrict__>;
+// metas whose item takes no part in the half-size scalar phase
+template <bool MSG>
+constexpr uint32_t kPrepNoScalars = MSG ? (kPrepFallback | kPrepVoid) : kPrepFallback;
+
+// The prepass role of a message instantiation: ITEMS items from `base` on, item
+// base + l on lane l, records to srec (SoA, row stride ITEMS).  ALL 64 LANES of
+// the wave call this: msg_hash_lane shuffles, votes and stages the wave's loads
+// cooperatively.  A lane that owns no item hashes one of its own block again
+// (base + lane % ITEMS, clamped to n - 1) and stores nothing, so the
+// wave-uniform fast paths are decided by the block's real items, the trip count
+// is the block's longest message, and no lane reads outside a message of the
+// block.
+template <int WA, uint32_t ITEMS>
+__device__ __forceinline__ void small_msg_prepass(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig,
+                                                  uint64_t sig_stride, const MsgRange &m, uint64_t msg_stride,
+                                                  uint32_t base, uint32_t n, uint32_t lane, uint32_t *srec,
+                                                  int lat_bits) {
+  static_assert(ITEMS >= 1 && ITEMS <= 64, "one lane per item of the block");
+  __shared__ uint4 stage[64 * kMsgQ];
+  const uint32_t own = base + lane % ITEMS;
+  const uint32_t li = own < n ? own : n - 1u;
+  uint32_t hw[16], s[8];
+  const bool ok = msg_hash_lane(pk, pk_stride, sig, sig_stride, m.msgs, m.offsets, m.msg_len, msg_stride, li, lane,
+                                stage, hw);
+  const uint4 *sigq = reinterpret_cast<const uint4 *>(sig + (uint64_t)li * sig_stride);
+  const uint4 s0 = sigq[2], s1 = sigq[3];
+  s[0] = s0.x; s[1] = s0.y; s[2] = s0.z; s[3] = s0.w;
+  s[4] = s1.x; s[5] = s1.y; s[6] = s1.z; s[7] = s1.w;
+  if (lane < ITEMS) (void)prep_from_hash<WA, PutPlain, true>(hw, s, srec + lane, ITEMS, lat_bits, !ok);
+}
+
+// The full-length path of a fallback item of a message instantiation: k mod l
+// from words 10..17 of its record (rec = the item's column, row stride stride).
+template <int WA, int CB, class VT>
+__device__ __forceinline__ uint32_t small_msg_fallback(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig,
+                                                       uint64_t sig_stride, uint32_t li, const uint32_t *rec,
+                                                       uint32_t stride, const uint32_t *tb, VT &vt) {
+  uint32_t pkw[8], sigw[16];
+  const uint4 *p = reinterpret_cast<const uint4 *>(pk + (uint64_t)li * pk_stride);
+  const uint4 *s = reinterpret_cast<const uint4 *>(sig + (uint64_t)li * sig_stride);
+  HSV_UNROLL
+  for (int j = 0; j < 2; ++j) {
+    const uint4 v = p[j];
+    pkw[4 * j] = v.x; pkw[4 * j + 1] = v.y; pkw[4 * j + 2] = v.z; pkw[4 * j + 3] = v.w;
+  }
+  HSV_UNROLL
+  for (int j = 0; j < 4; ++j) {
+    const uint4 v = s[j];
+    sigw[4 * j] = v.x; sigw[4 * j + 1] = v.y; sigw[4 * j + 2] = v.z; sigw[4 * j + 3] = v.w;
+  }
+  sc k;
+  HSV_UNROLL
+  for (int i = 0; i < 8; ++i) k.v[i] = rec[(10 + i) * stride];
+  return verify_one_full_comb<WA, false, CB>(pkw, sigw, k, tb, vt);
+}
+
 // Latency form in ONE launch (default at <= kPairMax items): a block of three
 // waves takes 64 items.  Waves 0 and 1 run the pair form's point phase (two
 // lanes per item: decompress R or A, build its table) while wave 2 runs the
@@ -317,10 +393,10 @@ hsv_verify_pair_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const
 // waves read their scalars from LDS.  Fallback items run the full-length path
 // on both lanes of their pair.
 constexpr int kFusedItems = 64;
-template <int WA, int CB>
+template <int WA, int CB, bool MSG = false>
 __global__ void __launch_bounds__(3 * 64)
 hsv_verify_pair_fused_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const uint8_t *__restrict__ sig,
-                             uint64_t sig_stride, const uint8_t *__restrict__ msg, uint64_t msg_stride, uint32_t n,
+                             uint64_t sig_stride, SmallMsgArg<MSG> msg, uint64_t msg_stride, uint32_t n,
                              uint8_t *__restrict__ flags_out, uint32_t *__restrict__ strict_bits,
                              uint4 *__restrict__ vt_ws, const uint32_t *__restrict__ comb_b, int lat_bits,
                              uint32_t *__restrict__ canary, uint32_t nonce, uint32_t inject,
@@ -336,10 +412,15 @@ hsv_verify_pair_fused_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride,
   if (wave < 2) canary[slot] = inject == kInjectCanary ? ~nonce : nonce;
   uint32_t ok = 0, small = 0;
   if (wave == 2) {
-    const uint32_t li = base + lane < n ? base + lane : n - 1u;
-    uint32_t pkw[8], sigw[16], msgw[8];
-    load_triple(pk, pk_stride, sig, sig_stride, msg, msg_stride, li, pkw, sigw, msgw);
-    (void)prep_scalars<WA>(pkw, sigw, msgw, srec + lane, kFusedItems, lat_bits);
+    if constexpr (MSG) {
+      small_msg_prepass<WA, kFusedItems>(pk, pk_stride, sig, sig_stride, msg, msg_stride, base, n, lane, srec,
+                                         lat_bits);
+    } else {
+      const uint32_t li = base + lane < n ? base + lane : n - 1u;
+      uint32_t pkw[8], sigw[16], msgw[8];
+      load_triple(pk, pk_stride, sig, sig_stride, msg, msg_stride, li, pkw, sigw, msgw);
+      (void)prep_scalars<WA>(pkw, sigw, msgw, srec + lane, kFusedItems, lat_bits);
+    }
   } else {
     const uint32_t li = item < n ? item : n - 1u;
     uint32_t pkw[8], rw[8];
@@ -359,13 +440,19 @@ hsv_verify_pair_fused_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride,
   uint32_t f;
   const uint32_t li = item < n ? item : n - 1u;
   if (meta & kPrepFallback) {
-    uint32_t pkw[8], sigw[16], msgw[8];
-    load_triple(pk, pk_stride, sig, sig_stride, msg, msg_stride, li, pkw, sigw, msgw);
-    f = verify_one_full_comb<WA, false, CB>(pkw, sigw, msgw, comb_b, vt);
+    if constexpr (MSG) {
+      f = small_msg_fallback<WA, CB>(pk, pk_stride, sig, sig_stride, li, srec + il, kFusedItems, comb_b, vt);
+    } else {
+      uint32_t pkw[8], sigw[16], msgw[8];
+      load_triple(pk, pk_stride, sig, sig_stride, msg, msg_stride, li, pkw, sigw, msgw);
+      f = verify_one_full_comb<WA, false, CB>(pkw, sigw, msgw, comb_b, vt);
+    }
   } else {
+    // (a void item's record holds the scalars of the empty message: computed and discarded)
     f = pair_scalar_phase<WA, CB>(p, ok, small, srec + il, kFusedItems, meta, comb_b, vt);
   }
   report_faults(fault, ((f & kFault) ? 1u : 0u) | (canary[slot] != nonce ? 2u : 0u));
+  if constexpr (MSG) f = (meta & kPrepVoid) ? 0u : f;
   if (item < n && p == 0u) {
     if (flags_out) flags_out[item] = (uint8_t)f;
     if (strict_bits && (f & kStrictOk)) atomicOr(&strict_bits[item >> 5], 1u << (item & 31u));
@@ -389,10 +476,10 @@ hsv_verify_pair_fused_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride,
 constexpr int kRowRows = 12;
 template <int RR>
 constexpr int kRowItemsOf = kRowRows / (2 * RR);
-template <int WA, int CB, int RR>
+template <int WA, int CB, int RR, bool MSG = false>
 __global__ void __launch_bounds__(4 * 64)
 hsv_verify_row_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const uint8_t *__restrict__ sig,
-                      uint64_t sig_stride, const uint8_t *__restrict__ msg, uint64_t msg_stride, uint32_t n,
+                      uint64_t sig_stride, SmallMsgArg<MSG> msg, uint64_t msg_stride, uint32_t n,
                       uint8_t *__restrict__ flags_out, uint32_t *__restrict__ strict_bits,
                       uint4 *__restrict__ vt_ws, const uint32_t *__restrict__ comb_b, int lat_bits,
                       uint32_t *__restrict__ canary, uint32_t nonce, uint32_t inject, uint32_t *__restrict__ fault) {
@@ -405,7 +492,10 @@ hsv_verify_row_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const 
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
   const uint32_t base = blockIdx.x * kRowItems;
   if (wave == 3) {
-    if (lane < (uint32_t)kRowItems) {
+    if constexpr (MSG) {
+      small_msg_prepass<WA, (uint32_t)kRowItems>(pk, pk_stride, sig, sig_stride, msg, msg_stride, base, n, lane, srec,
+                                                 lat_bits);
+    } else if (lane < (uint32_t)kRowItems) {
       const uint32_t li = base + lane < n ? base + lane : n - 1u;
       uint32_t pkw[8], sigw[16], msgw[8];
       load_triple(pk, pk_stride, sig, sig_stride, msg, msg_stride, li, pkw, sigw, msgw);
@@ -443,12 +533,17 @@ hsv_verify_row_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const 
   if (meta & kPrepFallback) {
     if (role == 0u && L.k == 0u && lead) {
       GlobalVarTab<kEnt> vt{vt_ws + (uint64_t)slot * vt_lane_uint4<WA>(), inject};
-      uint32_t pkw[8], sigw[16], msgw[8];
-      load_triple(pk, pk_stride, sig, sig_stride, msg, msg_stride, li, pkw, sigw, msgw);
-      f = verify_one_full_comb<WA, false, CB>(pkw, sigw, msgw, comb_b, vt);
+      if constexpr (MSG) {
+        f = small_msg_fallback<WA, CB>(pk, pk_stride, sig, sig_stride, li, srec + il, kRowItems, comb_b, vt);
+      } else {
+        uint32_t pkw[8], sigw[16], msgw[8];
+        load_triple(pk, pk_stride, sig, sig_stride, msg, msg_stride, li, pkw, sigw, msgw);
+        f = verify_one_full_comb<WA, false, CB>(pkw, sigw, msgw, comb_b, vt);
+      }
       bad = (f & kFault) ? 1u : 0u;
     }
   } else {
+    // (a void item's record holds the scalars of the empty message: computed and discarded)
     uint32_t d[5];
     HSV_UNROLL
     for (int i = 0; i < 5; ++i) d[i] = srec[(i + 5 * (int)role) * kRowItems + il];
@@ -475,6 +570,7 @@ hsv_verify_row_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const 
     bad = (a_ok & r_ok & (sane ^ 1u)) ? 1u : 0u;
   }
   report_faults(fault, bad | nc | (canary[slot] != nonce ? 2u : 0u));
+  if constexpr (MSG) f = (meta & kPrepVoid) ? 0u : f;
   if (item < n && role == 0u && L.k == 0u && lead) {
     if (flags_out) flags_out[item] = (uint8_t)f;
     if (strict_bits && (f & kStrictOk)) atomicOr(&strict_bits[item >> 5], 1u << (item & 31u));
@@ -524,10 +620,10 @@ __device__ uint64_t g_quad_clk[4][9];  // slot 8: the wave's HW_ID (SIMD_ID in b
   do {                        \
   } while (0)
 #endif
-template <int WA, int CB>
+template <int WA, int CB, bool MSG = false>
 __global__ void __launch_bounds__(4 * 64)
 hsv_verify_quad_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const uint8_t *__restrict__ sig,
-                       uint64_t sig_stride, const uint8_t *__restrict__ msg, uint64_t msg_stride, uint32_t n,
+                       uint64_t sig_stride, SmallMsgArg<MSG> msg, uint64_t msg_stride, uint32_t n,
                        uint8_t *__restrict__ flags_out, uint32_t *__restrict__ strict_bits,
                        uint4 *__restrict__ vt_ws, const uint32_t *__restrict__ comb_b, int lat_bits,
                        uint32_t *__restrict__ canary, uint32_t nonce, uint32_t inject, uint32_t *__restrict__ fault) {
@@ -548,7 +644,11 @@ hsv_verify_quad_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const
     // are built, each helper adds the low kQuadLo windows of one scalar over
     // its table (wave 2: c1 over -R, then the whole wide B comb over b; wave
     // 3: |c0| over -A) while the point waves run the high windows
-    if (wave == 2u && lane == 0u) {
+    if constexpr (MSG) {
+      // every lane of wave 2 hashes the block's one message; lane 0 stores the record
+      if (wave == 2u)
+        small_msg_prepass<WA, 1u>(pk, pk_stride, sig, sig_stride, msg, msg_stride, item, n, lane, srec, lat_bits);
+    } else if (wave == 2u && lane == 0u) {
       uint32_t pkw[8], sigw[16], msgw[8];
       load_triple(pk, pk_stride, sig, sig_stride, msg, msg_stride, li, pkw, sigw, msgw);
       (void)prep_scalars<WA>(pkw, sigw, msgw, srec, 1, lat_bits);
@@ -557,7 +657,7 @@ hsv_verify_quad_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const
     __syncthreads();
     HSV_QUAD_CLK(wave, 3);
     const uint32_t meta = srec[kPrepWords - 1];
-    if (!(meta & kPrepFallback)) {
+    if (!(meta & kPrepNoScalars<MSG>)) {
       const QuadLane L;
       const uint32_t h = wave - 2u;  // 0: R, 1: A
       uint32_t d[5];
@@ -605,7 +705,7 @@ hsv_verify_quad_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const
   const uint32_t meta = srec[kPrepWords - 1];
   uint32_t f = 0, bad = 0;
   qp_ext q{};
-  if (!(meta & kPrepFallback)) {
+  if (!(meta & kPrepNoScalars<MSG>)) {
     uint32_t d[5];
     HSV_UNROLL
     for (int i = 0; i < 5; ++i) d[i] = srec[i + 5 * (int)role];
@@ -628,11 +728,17 @@ hsv_verify_quad_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const
   if (meta & kPrepFallback) {
     if (lane == 0u) {
       GlobalVarTab<kEnt> vt{vt_ws + (uint64_t)slot * vt_lane_uint4<WA>(), inject};
-      uint32_t pkw[8], sigw[16], msgw[8];
-      load_triple(pk, pk_stride, sig, sig_stride, msg, msg_stride, li, pkw, sigw, msgw);
-      f = verify_one_full_comb<WA, false, CB>(pkw, sigw, msgw, comb_b, vt);
+      if constexpr (MSG) {
+        f = small_msg_fallback<WA, CB>(pk, pk_stride, sig, sig_stride, li, srec, 1, comb_b, vt);
+      } else {
+        uint32_t pkw[8], sigw[16], msgw[8];
+        load_triple(pk, pk_stride, sig, sig_stride, msg, msg_stride, li, pkw, sigw, msgw);
+        f = verify_one_full_comb<WA, false, CB>(pkw, sigw, msgw, comb_b, vt);
+      }
       bad = (f & kFault) ? 1u : 0u;
     }
+  } else if (MSG && (meta & kPrepVoid)) {
+    // a void item: no wave ran its scalar phase, nothing was handed over; f = 0
   } else {
     // Q = the R wave's sum + the A wave's + the helpers' (cached forms from LDS)
     q = q_add_op(q, q_op_of_cached(sq_a, L), L);
@@ -678,10 +784,10 @@ constexpr int kJointLo = 7;
 #define HSV_JOINT_MAX 768
 #endif
 constexpr uint32_t kJointMax = HSV_JOINT_MAX;
-template <int WA, int CB>
+template <int WA, int CB, bool MSG = false>
 __global__ void __launch_bounds__((kJointItems + 1) * 64)
 hsv_verify_joint_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const uint8_t *__restrict__ sig,
-                        uint64_t sig_stride, const uint8_t *__restrict__ msg, uint64_t msg_stride, uint32_t n,
+                        uint64_t sig_stride, SmallMsgArg<MSG> msg, uint64_t msg_stride, uint32_t n,
                         uint8_t *__restrict__ flags_out, uint32_t *__restrict__ strict_bits,
                         uint4 *__restrict__ vt_ws, const uint32_t *__restrict__ comb_b, int lat_bits,
                         uint32_t *__restrict__ canary, uint32_t nonce, uint32_t inject, uint32_t *__restrict__ fault) {
@@ -697,7 +803,9 @@ hsv_verify_joint_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, cons
   if (wave == K) {
     // the items' scalar prepasses on lanes 0..K-1, then each item's whole
     // wide B comb (16 additions) while the point waves run their Straus loops
-    if (lane < K) {
+    if constexpr (MSG) {
+      small_msg_prepass<WA, K>(pk, pk_stride, sig, sig_stride, msg, msg_stride, base, n, lane, srec, lat_bits);
+    } else if (lane < K) {
       const uint32_t li = base + lane < n ? base + lane : n - 1u;
       uint32_t pkw[8], sigw[16], msgw[8];
       load_triple(pk, pk_stride, sig, sig_stride, msg, msg_stride, li, pkw, sigw, msgw);
@@ -709,7 +817,7 @@ hsv_verify_joint_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, cons
     HSV_NOUNROLL
     for (uint32_t t = 0; t < K; ++t) {
       const uint32_t meta_t = srec[(kPrepWords - 1) * K + t];
-      if (meta_t & kPrepFallback) continue;
+      if (meta_t & kPrepNoScalars<MSG>) continue;
       // the low kJointLo windows of the item's two scalars over its tables,
       // then its whole wide B comb onto that sum
       uint32_t d1[5], d0[5], b[8];
@@ -769,7 +877,7 @@ hsv_verify_joint_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, cons
   const uint32_t a_ok = __builtin_amdgcn_readlane(ok, 32), small_a = __builtin_amdgcn_readlane(small, 32);
   uint32_t f = 0, bad = 0;
   qp_ext q{};
-  if (!(meta & kPrepFallback)) {
+  if (!(meta & kPrepNoScalars<MSG>)) {
     uint32_t d1[5], d0[5];
     HSV_UNROLL
     for (int i = 0; i < 5; ++i) {
@@ -782,11 +890,17 @@ hsv_verify_joint_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, cons
   if (meta & kPrepFallback) {
     if (lane == 0u) {
       GlobalVarTab<kEnt> vt{vt_ws + (uint64_t)slot * vt_lane_uint4<WA>(), inject};
-      uint32_t pkw[8], sigw[16], msgw[8];
-      load_triple(pk, pk_stride, sig, sig_stride, msg, msg_stride, li, pkw, sigw, msgw);
-      f = verify_one_full_comb<WA, false, CB>(pkw, sigw, msgw, comb_b, vt);
+      if constexpr (MSG) {
+        f = small_msg_fallback<WA, CB>(pk, pk_stride, sig, sig_stride, li, srec + wave, K, comb_b, vt);
+      } else {
+        uint32_t pkw[8], sigw[16], msgw[8];
+        load_triple(pk, pk_stride, sig, sig_stride, msg, msg_stride, li, pkw, sigw, msgw);
+        f = verify_one_full_comb<WA, false, CB>(pkw, sigw, msgw, comb_b, vt);
+      }
       bad = (f & kFault) ? 1u : 0u;
     }
+  } else if (MSG && (meta & kPrepVoid)) {
+    // a void item: neither wave ran its scalar phase, nothing was handed over; f = 0
   } else {
     q = q_add_op(q, q_op_of_cached(sq_b[wave], L), L);
     const RowLane &R = L;
@@ -1136,37 +1250,64 @@ constexpr uint32_t row_max() { return kRowMaxDefault; }
 //   joint (<= kJointMax): kJointItems items per block, a slot per point wave;
 //   row   (<= row_max()): see above, a slot per row;
 //   pair  (<= kPairMax): see above, a slot per pair lane.
-template <int WA, int CB>
+// MSG: the message instantiations (hsv_launch_verify_msgs), the same grids,
+// blocks and slots.  Their cut-overs are constants of their own beside the
+// digest path's, set from profiles/msgs_small_latency.json: at
+// every measured size and length the form chosen here has a p50 no higher than
+// the two-launch form's in the same run, so none of them moved.  p50 of a
+// device call + synchronise, this form / two launches, 32-byte and ragged
+// 0..1024-byte messages: quad 0.117 / 0.693 and 0.192 / 0.767 ms at 256 items;
+// joint 0.127 / 0.694 and 0.215 / 0.768 at 257, 0.132 / 0.698 and 0.212 / 0.773
+// at 768; row 0.212 / 0.699 and 0.295 / 0.774 at 769, 0.349 / 0.713 and 0.401 /
+// 0.803 at 3072; pair 0.457 / 0.714 and 0.505 / 0.803 at 3073, 0.469 / 0.733
+// and 0.523 / 0.829 at 8192.  The choice depends on n alone: in the
+// device form the lengths live in device memory, and a long message costs its
+// one lane the same serial hash in either route.  `force` (1 quad, 2 joint,
+// 3 row, 4 pair; 0 = by n) is the test library's hsv_test_msgs_small.
+constexpr uint32_t kMsgQuadMax = hsv::kQuadMax;
+constexpr uint32_t kMsgJointMax = hsv::kJointMax;
+constexpr uint32_t kMsgRowMax = kRowMaxDefault;
+enum SmallFormId : int { kFormQuad = 1, kFormJoint = 2, kFormRow = 3, kFormPair = 4 };
+
+template <int WA, int CB, bool MSG = false>
 struct SmallForm {
-  decltype(&hsv::hsv_verify_quad_kernel<WA, CB>) kern;
+  decltype(&hsv::hsv_verify_quad_kernel<WA, CB, MSG>) kern;
   uint32_t grid, block;
   size_t slots;
-  explicit SmallForm(uint32_t n) {
-    if (n <= hsv::kQuadMax) {
-      kern = hsv::hsv_verify_quad_kernel<WA, CB>;
+  int id;
+  explicit SmallForm(uint32_t n, int force = 0) {
+    id = force                                        ? force
+         : n <= (MSG ? kMsgQuadMax : hsv::kQuadMax)   ? kFormQuad
+         : n <= (MSG ? kMsgJointMax : hsv::kJointMax) ? kFormJoint
+         : n <= (MSG ? kMsgRowMax : row_max())        ? kFormRow
+                                                      : kFormPair;
+    if (id == kFormQuad) {
+      kern = hsv::hsv_verify_quad_kernel<WA, CB, MSG>;
       grid = n, block = 4 * 64, slots = (size_t)grid * 2u;
-    } else if (n <= hsv::kJointMax) {
-      kern = hsv::hsv_verify_joint_kernel<WA, CB>;
+    } else if (id == kFormJoint) {
+      kern = hsv::hsv_verify_joint_kernel<WA, CB, MSG>;
       grid = (n + hsv::kJointItems - 1) / hsv::kJointItems, block = (hsv::kJointItems + 1) * 64;
       slots = (size_t)grid * hsv::kJointItems;
-    } else if (n <= row_max()) {
-      kern = hsv::hsv_verify_row_kernel<WA, CB, 1>;
+    } else if (id == kFormRow) {
+      kern = hsv::hsv_verify_row_kernel<WA, CB, 1, MSG>;
       grid = (n + hsv::kRowItemsOf<1> - 1) / hsv::kRowItemsOf<1>, block = 4 * 64;
       slots = (size_t)grid * hsv::kRowRows;
     } else {
-      kern = hsv::hsv_verify_pair_fused_kernel<WA, CB>;
+      kern = hsv::hsv_verify_pair_fused_kernel<WA, CB, MSG>;
       grid = (n + hsv::kFusedItems - 1) / hsv::kFusedItems, block = 3 * 64;
       slots = (size_t)grid * 2u * hsv::kFusedItems;
     }
   }
 };
 
-template <int WA, int CB>
+template <int WA, int CB, bool MSG = false>
 hipError_t launch_small(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, uint64_t sig_stride,
-                        const uint8_t *msg, uint64_t msg_stride, uint32_t n, uint8_t *flags_out,
+                        hsv::SmallMsgArg<MSG> msg, uint64_t msg_stride, uint32_t n, uint8_t *flags_out,
                         uint32_t *strict_bits, const uint32_t *comb_b, uint32_t *fault, hipStream_t stream,
-                        void *ws_in = nullptr, size_t ws_cap = 0, size_t *ws_need = nullptr) {
-  const SmallForm<WA, CB> f(n);
+                        void *ws_in = nullptr, size_t ws_cap = 0, size_t *ws_need = nullptr, int force = 0,
+                        int *form_id = nullptr) {
+  const SmallForm<WA, CB, MSG> f(n, force);
+  if (form_id) *form_id = f.id;
   const size_t ws_bytes = f.slots * hsv::vt_lane_uint4<WA>() * sizeof(uint4);
   const size_t need = ws_bytes + f.slots * sizeof(uint32_t);
   if (ws_need) {  // size query only
@@ -1255,9 +1396,32 @@ extern "C" hipError_t hsv_launch_verify_tx(int variant, const uint8_t *txs, cons
                            comb_b, fault, stream);
 }
 
-// Messages of any length: the message prepass, then the point pass that reads
-// k from the record for fallback items.  Two ordinary launches at every n (no
-// latency form hashes more than 32 bytes).
+namespace {
+// How hsv_launch_verify_msgs routes n <= kPairMax items: -1 the small form
+// SmallForm picks by n (the default), 0 the two launches of larger batches
+// (the parent's behaviour, for A/B runs), 1..4 one small form at every such n.
+// A measurement switch, so only libhsv_test.so can move it (hsvi_set_msgs_small
+// behind hsv_test_msgs_small): the product library reads no environment
+// variable for it (tests/test_capi.py keeps that list closed).
+std::atomic<int> g_msgs_small{-1};
+// launches so far by form: two-launch, quad, joint, row, pair
+std::atomic<uint64_t> g_msgs_forms[5];
+}  // namespace
+
+extern "C" int hsvi_set_msgs_small(int mode) {
+  if (mode < -1 || mode > kFormPair) return -2;
+  return g_msgs_small.exchange(mode);
+}
+
+extern "C" int hsvi_msgs_form_counts(uint64_t out[5]) {
+  for (int i = 0; i < 5; ++i) out[i] = g_msgs_forms[i].load();
+  return 0;
+}
+
+// Messages of any length.  At <= kPairMax items one launch of a small form's
+// message instantiation, whose prepass wave hashes the whole messages beside
+// the point waves; above, the message prepass, then the point
+// pass that reads k from the record for fallback items.
 extern "C" hipError_t hsv_launch_verify_msgs(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig,
                                              uint64_t sig_stride, const uint8_t *msgs, const uint64_t *offsets,
                                              uint64_t msg_len, uint64_t msg_stride, uint32_t n, uint8_t *flags_out,
@@ -1265,6 +1429,16 @@ extern "C" hipError_t hsv_launch_verify_msgs(const uint8_t *pk, uint64_t pk_stri
                                              hipStream_t stream) {
   if (n == 0) return hipSuccess;
   if (!comb16 || !fault) return hipErrorInvalidValue;
+  const int mode = g_msgs_small.load();
+  if (mode != 0 && n <= kPairMax) {
+    int id = 0;
+    const hipError_t e = launch_small<4, 16, true>(pk, pk_stride, sig, sig_stride, hsv::MsgRange{msgs, offsets, msg_len},
+                                                   msg_stride, n, flags_out, strict_bits, comb16, fault, stream,
+                                                   nullptr, 0, nullptr, mode > 0 ? mode : 0, &id);
+    g_msgs_forms[id].fetch_add(1);
+    return e;
+  }
+  g_msgs_forms[0].fetch_add(1);
   const MsgPrep mp{msgs, offsets, msg_len, msg_stride};
   return launch_hp<4, HSV_HP_WAVES, 16>(pk, pk_stride, sig, sig_stride, nullptr, 0, n, flags_out, strict_bits, comb16,
                                         fault, stream, nullptr, nullptr, 0, nullptr, &mp);

@@ -11,9 +11,11 @@
 //                         with k mod l in their b words;
 //   hsv_verify_hp_kernel  (hsv_kernels.hip, KREC instantiation) the point
 //                         pass; it never reads a message byte.
-// Two ordinary launches at every n and no inter-workgroup waiting: a message of
-// many megabytes keeps one wave of the prepass busy and nothing polls for it
-// (DESIGN.md 4e).
+// Two ordinary launches above 2^13 items and no inter-workgroup waiting: a
+// message of many megabytes keeps one wave of the prepass busy and nothing
+// polls for it.  At or below 2^13 items the small forms of
+// hsv_kernels.hip run instead, one launch, their prepass wave hashing through
+// the same msg_hash_lane.
 #include <hip/hip_runtime.h>
 
 #define HSV_SHA_BITOP3 1  // v_bitop3_b32 in the message hash, as hsv_mempool.hip

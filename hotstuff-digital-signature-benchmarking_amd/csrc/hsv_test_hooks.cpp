@@ -79,6 +79,8 @@ int hsv_test_signer_group(int g) { return hsvi_set_signer_group(g); }
 size_t hsv_test_tx_sign_chunk(size_t items) { return hsvi_set_tx_sign_chunk(items); }
 int hsv_test_committee_tx_counts(uint64_t out[3]) { return hsvh::committee_tx_counts(out); }
 int hsv_test_committee_msgs_counts(uint64_t out[3]) { return hsvh::committee_msgs_counts(out); }
+int hsv_test_msgs_small(int mode) { return hsvi_set_msgs_small(mode); }
+int hsv_test_msgs_form_counts(uint64_t out[5]) { return hsvi_msgs_form_counts(out); }
 size_t hsv_test_stage_bytes(size_t bytes) { return hsvh::g_stage_bytes.exchange(bytes ? bytes : hsvh::kStageBytes); }
 
 }  // extern "C"

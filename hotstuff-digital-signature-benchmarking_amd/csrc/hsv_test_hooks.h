@@ -102,6 +102,16 @@ HSV_API int hsv_test_committee_tx_counts(uint64_t out[3]);
  * call (items instead of transactions).  The two hooks keep slots of their
  * own: a call of one kind leaves the other hook's answer as it was. */
 HSV_API int hsv_test_committee_msgs_counts(uint64_t out[3]);
+/* Tests and measurement (tools/msgs_small_bench.py): how hsv_verify_msgs*
+ * verifies a launch of at most 2^13 items.  -1 = the small form of that size
+ * (the default); 0 = the message prepass and the point pass, two launches, as
+ * larger batches; 1, 2, 3, 4 = the quad, joint, row, pair form at every such
+ * size.  Process-wide; the product library has no such switch.  Returns the
+ * previous mode, or -2 for an unknown one.  Needs no device. */
+HSV_API int hsv_test_msgs_small(int mode);
+/* Launches of hsv_verify_msgs* in this process so far, by form: out[0]
+ * two-launch, out[1] quad, out[2] joint, out[3] row, out[4] pair.  HSV_OK. */
+HSV_API int hsv_test_msgs_form_counts(uint64_t out[5]);
 
 #ifdef __cplusplus
 }
