@@ -13,7 +13,8 @@
 //
 // Table layout: entry (j, m) at word ((j * 128) + m - 1) * 24 of a key's
 // table; 24 words = y+x, y-x, 2dxy, each a canonical 8-word encoding.
-// A key's table is 32 * 128 * 96 B = 384 KiB.
+// A key's table is 32 * 128 * 96 B = 384 KiB.  The compact form at the end of
+// this file trades additions for memory: 4-bit digits, 48 KiB per key.
 #pragma once
 #include "hsv_point.hpp"
 #include "hsv_scalar.hpp"
@@ -282,6 +283,132 @@ HSV_INL uint32_t verify_one_comb_k(uint32_t key_flags, const uint32_t sig[16], c
   return (strict_ok ? kStrictOk : 0u) | (eq_ok ? kEqOk : 0u) | (parse_ok ? kParseOk : 0u) |
          (small_a ? kSmallA : 0u) | (small_r ? kSmallR : 0u) | (s_ok ? kSOk : 0u) |
          (a_ok ? kAOk : 0u) | (r_ok ? kROk : 0u) | fault_bit(a_ok, r_ok, q);
+}
+
+// ---- compact tables: 4-bit signed digits (HSV_COMMITTEE_DIGITS_COMPACT) --------
+// The same comb with radix 16:
+//   T4[j][m] = [m * 16^j](-A),   j in [0, 64), m in [1, 8]   (affine Niels)
+// and the signed digits of k + C4, C4 = sum 8 * 16^j, each in [-8, 7].
+// k < l < 2^253 and C4 < 2^256 * 8 / 15, so the sum stays below 2^256 and the
+// top digit never carries out.  Entry (j, m) at word ((j * 8) + m - 1) * 24 of
+// a key's table, the 24-word format above: 64 * 8 * 96 B = 48 KiB per key,
+// an eighth of the full table, for 64 additions for [k](-A) instead of 32.
+constexpr int kComb4Pos = 64;
+constexpr int kComb4Ent = 8;
+constexpr uint64_t kComb4TableWords = (uint64_t)kComb4Pos * kComb4Ent * kCombEntryWords;  // per key
+
+// The builder gives a lane a run of 16 positions, 128 entries, under one
+// batched inversion: at one position (8 entries) per inversion the build
+// would be inversion-bound (~265 products against 8 * ~14); at 128 entries the
+// inversion is an eighth of the lane's work, as in comb_build_position, and
+// the scratch per lane (128 * 8 words) is comb_build_position's too.
+constexpr int kComb4GroupPos = 16;
+constexpr int kComb4Groups = kComb4Pos / kComb4GroupPos;   // lanes per key
+constexpr int kComb4GroupEnt = kComb4GroupPos * kComb4Ent;  // entries per inversion
+
+// Group g of one key's compact table: positions [16g, 16g + 16) of the table
+// at `table`, for the decompressed affine (x, y), negated when neg.  The base
+// of a position is twice the previous position's eighth multiple.
+HSV_INL void comb4_build_group(const fe &x, const fe &y, uint32_t neg, int g, uint32_t *table, uint32_t *tmp) {
+  uint32_t *out = table + (uint64_t)g * kComb4GroupEnt * kCombEntryWords;
+  ge_ext acc = comb_position_base(x, y, neg, 8 * g);  // [16^(16g)]P: 64g doublings
+  ge_cached bc = ge_to_cached(acc);
+  fe pp = fe_small(1);
+  HSV_NOUNROLL
+  for (int i = 0; i < kComb4GroupEnt; ++i) {
+    if (i % kComb4Ent != 0) {
+      acc = ge_add_cached<true>(acc, bc);
+    } else if (i != 0) {
+      acc = ge_dbl<true>(acc);  // [16]base = 2 * [8]base
+      bc = ge_to_cached(acc);
+    }
+    uint32_t *e = out + i * kCombEntryWords;
+    fe_pack(acc.X, e);
+    fe_pack(acc.Y, e + 8);
+    fe_pack(acc.Z, e + 16);
+    pp = fe_mul(pp, acc.Z);
+    fe_pack(pp, tmp + i * 8);
+  }
+  fe inv = fe_invert(pp);
+  HSV_NOUNROLL
+  for (int i = kComb4GroupEnt - 1; i >= 0; --i) {
+    uint32_t *e = out + i * kCombEntryWords;
+    const fe X = fe_from_words_masked(e), Y = fe_from_words_masked(e + 8), Z = fe_from_words_masked(e + 16);
+    fe zinv = inv;
+    if (i > 0) {
+      zinv = fe_mul(inv, fe_from_words_masked(tmp + (i - 1) * 8));
+      inv = fe_mul(inv, Z);
+    }
+    const fe ax = fe_mul(X, zinv), ay = fe_mul(Y, zinv);
+    fe_pack(fe_add(ay, ax), e);
+    fe_pack(fe_sub(ay, ax), e + 8);
+    fe_pack(fe_mul(fe_mul(ax, ay), fe_d2()), e + 16);
+  }
+}
+
+// verify_one_comb_k against a compact table ta.  [s]B comes from the wide comb
+// of B (tb16: 16-bit digits, 16 additions, the table the generic kernels read):
+// per step four key positions (the nibbles of 16 bits of k + C4) and one
+// position of B, 64 + 16 = 80 mixed additions in all.  With the 8-bit table of
+// B (32 additions, one per two key positions) the call measured 4 - 5 % slower
+// at 2^17 keys and 11 - 12 % slower at 1000.  The B entry is
+// selected before the first addition of a step and the key entries' addresses
+// depend on the digits alone, so no load waits for the accumulator.
+// Flags, key flags, fault_bit and inject (first key entry) as verify_one_comb_k.
+constexpr int kComb4PerB = kComb4Pos / kComb16Pos;  // key positions per position of B
+HSV_INL uint32_t verify_one_comb4_k(uint32_t key_flags, const uint32_t sig[16], const sc &k, const uint32_t *ta,
+                                    const uint32_t *tb16, uint32_t inject = kInjectNone) {
+  const uint32_t s_ok = sc_is_canonical(sig + 8);
+  uint32_t kr[9], sr[9];
+  recode_add<9, 4, kComb4Pos>(k.v, 8, kr);
+  recode_add<9, 16, kComb16Pos>(sig + 8, 8, sr);
+
+  ge_ext q = ge_identity();
+  HSV_NOUNROLL
+  for (int j = 0; j < kComb16Pos; ++j) {
+    const uint32_t ca = kr[0] & 0xffffu, cb = sr[0] & 0xffffu;
+    HSV_UNROLL
+    for (int i = 0; i < 8; ++i) {
+      kr[i] = (kr[i] >> 16) | (kr[i + 1] << 16);
+      sr[i] = (sr[i] >> 16) | (sr[i + 1] << 16);
+    }
+    kr[8] >>= 16;
+    sr[8] >>= 16;
+    const CombPosTab tpb{tb16 + (uint64_t)j * kComb16Ent * kCombEntryWords};
+    const ge_niels nb = select_niels<16>(tpb, cb);
+    HSV_UNROLL
+    for (int a = 0; a < kComb4PerB; ++a) {
+      const CombPosTab tp{ta + (uint64_t)(kComb4PerB * j + a) * kComb4Ent * kCombEntryWords};
+      ge_niels n = select_niels<4>(tp, (ca >> (4 * a)) & 0xfu);
+      if (inject != kInjectNone && j == 0 && a == 0) n = niels_injected(n, inject);
+      q = ge_add_niels<true>(q, n);
+    }
+    q = ge_add_niels<true>(q, nb);
+  }
+
+  fe rx, ry;
+  const uint32_t r_ok = ge_decompress(sig, rx, ry);
+  const uint32_t small_r = r_ok & y_is_small_order(ry);
+  const uint32_t same = ge_eq_affine(q, rx, ry);
+  const uint32_t a_ok = (key_flags & kKeyAOk) ? 1u : 0u;
+  const uint32_t small_a = a_ok & ((key_flags & kKeySmallA) ? 1u : 0u);
+
+  const uint32_t parse_ok = s_ok & a_ok & r_ok;
+  const uint32_t eq_ok = parse_ok & same;
+  const uint32_t strict_ok = eq_ok & (small_a ^ 1u) & (small_r ^ 1u);
+  return (strict_ok ? kStrictOk : 0u) | (eq_ok ? kEqOk : 0u) | (parse_ok ? kParseOk : 0u) |
+         (small_a ? kSmallA : 0u) | (small_r ? kSmallR : 0u) | (s_ok ? kSOk : 0u) |
+         (a_ok ? kAOk : 0u) | (r_ok ? kROk : 0u) | fault_bit(a_ok, r_ok, q);
+}
+
+// verify_one_comb against a compact table: the hash of (R, pk, 32-byte
+// digest), then the core above.
+HSV_INL uint32_t verify_one_comb4(const uint32_t pk[8], uint32_t key_flags, const uint32_t sig[16],
+                                  const uint32_t msg[8], const uint32_t *ta, const uint32_t *tb16,
+                                  uint32_t inject = kInjectNone) {
+  uint32_t h[16];
+  sha512_96(sig, pk, msg, h);
+  return verify_one_comb4_k(key_flags, sig, sc_reduce512(h), ta, tb16, inject);
 }
 
 }  // namespace hsv

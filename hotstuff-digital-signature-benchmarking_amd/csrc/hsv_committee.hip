@@ -13,6 +13,10 @@
 //  hsv_comb_verify_quad_fused_kernel  the same check for batches of at most
 //                          2^12 votes (QC latency): four lanes per vote for
 //                          the additions, R decompressed by a second wave.
+//  hsv_comb4_build_kernel, hsv_comb4_verify_kernel  the first two for compact
+//                          tables (4-bit digits, 48 KiB per key): one lane per
+//                          (key, 16 positions) builds, one lane per vote
+//                          verifies at every batch size (80 mixed additions).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -583,6 +587,52 @@ __global__ void __launch_bounds__(64) hsv_lanesplit_check_kernel(const uint32_t 
   if (r < rows && (threadIdx.x & (16u * kRows - 1u)) == 0u) out[r] |= bad << kShift;
 }
 
+// Compact (4-bit digit) tables, hsv_comb.hpp.  Build: one lane per (key,
+// group of 16 positions), the group wave-uniform (keys padded to a multiple of
+// 64 per group); key flags from group 0 as hsv_comb_build_kernel's position 0.
+__global__ void __launch_bounds__(256)
+hsv_comb4_build_kernel(const uint8_t *__restrict__ encs, uint32_t nkeys, uint32_t npad, uint32_t negate,
+                       uint32_t *__restrict__ tables, uint32_t *__restrict__ tmp,
+                       uint8_t *__restrict__ key_flags) {
+  const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t g = id / npad, key = id % npad;
+  if (g >= (uint32_t)kComb4Groups || key >= nkeys) return;
+  uint32_t w[8];
+  const uint4 *p = reinterpret_cast<const uint4 *>(encs + (uint64_t)key * 32);
+  const uint4 p0 = p[0], p1 = p[1];
+  w[0] = p0.x; w[1] = p0.y; w[2] = p0.z; w[3] = p0.w;
+  w[4] = p1.x; w[5] = p1.y; w[6] = p1.z; w[7] = p1.w;
+  fe x, y;
+  const uint32_t ok = ge_decompress(w, x, y);
+  if (g == 0 && key_flags) key_flags[key] = (uint8_t)((ok ? kKeyAOk : 0u) | (ok && y_is_small_order(y) ? kKeySmallA : 0u));
+  comb4_build_group(x, y, negate, (int)g, tables + (uint64_t)key * kComb4TableWords,
+                    tmp + (uint64_t)id * kComb4GroupEnt * 8);
+}
+
+// hsv_comb_verify_kernel against compact tables: one verification per lane at
+// every batch size (a compact committee has no latency form); comb16: the wide
+// comb of B.
+__global__ void __launch_bounds__(256, 2)
+hsv_comb4_verify_kernel(const uint32_t *__restrict__ key_idx, const uint8_t *__restrict__ sig,
+                        uint64_t sig_stride, const uint8_t *__restrict__ msg, uint64_t msg_stride,
+                        uint32_t m, const uint8_t *__restrict__ pks, const uint8_t *__restrict__ key_flags,
+                        uint32_t nkeys, const uint32_t *const *__restrict__ key_tables,
+                        const uint32_t *__restrict__ comb16, uint8_t *__restrict__ flags_out, uint32_t inject,
+                        uint32_t *__restrict__ fault) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const uint32_t kidx = key_idx[i];
+  const bool kvalid = kidx < nkeys;
+  const uint32_t kk = kvalid ? kidx : 0u;
+  uint32_t pkw[8], sigw[16], msgw[8];
+  load_vote_words(reinterpret_cast<const uint4 *>(pks + (uint64_t)kk * 32),
+                  reinterpret_cast<const uint4 *>(sig + (uint64_t)i * sig_stride),
+                  reinterpret_cast<const uint4 *>(msg + (uint64_t)i * msg_stride), pkw, sigw, msgw);
+  const uint32_t f = verify_one_comb4(pkw, key_flags[kk], sigw, msgw, key_tables[kk], comb16, inject);
+  if (f & kFault) fault[0] = 1u;  // device self-check (hsv_kernels.hip report_faults)
+  flags_out[i] = kvalid ? (uint8_t)f : (uint8_t)0;
+}
+
 // one lane per (position j, chunk c) of the wide B table; j is wave-uniform
 // (256 chunks per position)
 __global__ void __launch_bounds__(256) hsv_comb16_build_kernel(uint32_t *__restrict__ table,
@@ -651,6 +701,18 @@ extern "C" hipError_t hsv_launch_comb_build(const uint8_t *encs, uint32_t nkeys,
   return hipGetLastError();
 }
 
+// the compact tables of nkeys keys, contiguous at `tables` (hsv_comb4_table_bytes each)
+extern "C" hipError_t hsv_launch_comb4_build(const uint8_t *encs, uint32_t nkeys, uint32_t negate,
+                                             uint32_t *tables, uint32_t *tmp, uint8_t *key_flags,
+                                             hipStream_t stream) {
+  if (nkeys == 0) return hipSuccess;
+  const uint32_t npad = (nkeys + 63u) / 64u * 64u;
+  const uint32_t lanes = npad * (uint32_t)hsv::kComb4Groups;
+  hipLaunchKernelGGL(hsv::hsv_comb4_build_kernel, dim3((lanes + 255u) / 256u), dim3(256), 0, stream, encs,
+                     nkeys, npad, negate, tables, tmp, key_flags);
+  return hipGetLastError();
+}
+
 // batches up to this many votes take the four-lanes-per-vote form
 static constexpr uint32_t kCombQuadMax = 1u << 12;
 
@@ -661,11 +723,18 @@ static thread_local uint32_t *t_last_fault = nullptr;  // the calling thread's l
 extern "C" hipError_t hsv_launch_comb_verify(const uint32_t *key_idx, const uint8_t *sig, uint64_t sig_stride,
                                              const uint8_t *msg, uint64_t msg_stride, uint32_t m,
                                              const uint8_t *pks, const uint8_t *key_flags, uint32_t nkeys,
-                                             const uint32_t *const *key_tables, const uint32_t *btable,
-                                             uint8_t *flags_out, uint32_t *fault, uint32_t *done,
-                                             hipStream_t stream) {
+                                             const uint32_t *const *key_tables, int digit_bits,
+                                             const uint32_t *btable, uint8_t *flags_out, uint32_t *fault,
+                                             uint32_t *done, hipStream_t stream) {
   if (m == 0) return hipSuccess;
-  if (!fault) return hipErrorInvalidValue;
+  if (!fault || (digit_bits != 8 && digit_bits != 4)) return hipErrorInvalidValue;
+  if (digit_bits == 4) {  // compact tables: one lane per vote at every size, no markers; btable: the WIDE comb
+    if (done) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(hsv::hsv_comb4_verify_kernel, dim3((m + 255u) / 256u), dim3(256), 0, stream, key_idx, sig,
+                       sig_stride, msg, msg_stride, m, pks, key_flags, nkeys, key_tables, btable, flags_out,
+                       (uint32_t)hsvi_inject_mode(), fault);
+    return hipGetLastError();
+  }
 #ifdef HSV_QC_WAVE_CLOCKS
   t_last_fault = done ? fault : nullptr;
 #endif
@@ -701,6 +770,11 @@ extern "C" uint64_t hsv_comb_table_bytes(void) { return hsv::kCombTableWords * 4
 extern "C" uint64_t hsv_comb_tmp_bytes(uint32_t nkeys) {
   const uint64_t npad = (nkeys + 63u) / 64u * 64u;
   return npad * (uint64_t)hsv::kCombPos * hsv::kCombEnt * 8ull * 4ull;
+}
+extern "C" uint64_t hsv_comb4_table_bytes(void) { return hsv::kComb4TableWords * 4ull; }
+extern "C" uint64_t hsv_comb4_tmp_bytes(uint32_t nkeys) {
+  const uint64_t npad = (nkeys + 63u) / 64u * 64u;
+  return npad * (uint64_t)hsv::kComb4Groups * hsv::kComb4GroupEnt * 8ull * 4ull;
 }
 
 #ifdef HSV_QC_WAVE_CLOCKS

@@ -129,6 +129,7 @@ struct CommitteeDev {
   const uint8_t *d_pks = nullptr;
   const uint8_t *d_kflags = nullptr;
   const uint32_t *const *d_tabptr = nullptr;
+  int digit_bits = 8;  // width of the tables behind d_tabptr: 8, or 4 (compact, hsv_committee_create_ex)
 };
 
 // ---- resident latency service (on by default; HSV_QC_RESIDENT=0 turns it off) ------
@@ -474,8 +475,12 @@ int committee_run(const CommitteeDev &cd, const uint32_t *key_idx, const uint8_t
   DeviceGuard guard(c.device);
   if (guard.status() != hipSuccess) return hip_fail("hipSetDevice", guard.status());
   rc = ensure_btable(c);  // also after an hsv_shutdown
+  // compact tables have no latency form: no resident request, no zero-copy
+  // launch; their kernel takes [s]B from the wide comb of B
+  const bool compact = cd.digit_bits == 4;
+  if (rc == HSV_OK && compact) rc = ensure_btable16(c);
   if (rc != HSV_OK) return rc;
-  if (resident_enabled() && m <= hsv_comb_resident_votes()) {
+  if (!compact && resident_enabled() && m <= hsv_comb_resident_votes()) {
     rc = resident_run(cd, key_idx, sig, sig_stride, msg, msg_stride, m, flags_out, c.d_btable);
     if (rc != kResidentUnavailable) return rc;
   }
@@ -512,7 +517,7 @@ int committee_run(const CommitteeDev &cd, const uint32_t *key_idx, const uint8_t
     // before the kernel's completion signal (same box, alternating processes,
     // profiles/r04b_qc_ab_marker.txt: C1 0.0444 -> 0.0394 ms, C3 0.0587 ->
     // 0.0559 ms, one verify_strict 0.0443 -> 0.0395 ms).
-    const bool zero_copy = k <= kZeroCopyMax && s.h_buf_dev != nullptr;
+    const bool zero_copy = !compact && k <= kZeroCopyMax && s.h_buf_dev != nullptr;
     uint8_t *flags_h, *flags_d, *fault_h, *fault_d;
     uint32_t nmark = 0;
     volatile uint32_t *marks = nullptr;
@@ -545,7 +550,7 @@ int committee_run(const CommitteeDev &cd, const uint32_t *key_idx, const uint8_t
     if (e == hipSuccess)
       e = hsv_launch_comb_verify(reinterpret_cast<const uint32_t *>(dbuf + idx_off), dbuf + sig_off, 64,
                                  dbuf + msg_off, msg_stride ? 32 : 0, (uint32_t)k, cd.d_pks, cd.d_kflags, cd.n,
-                                 cd.d_tabptr, c.d_btable, flags_d, reinterpret_cast<uint32_t *>(fault_d), marks_d,
+                                 cd.d_tabptr, cd.digit_bits, compact ? c.d_btable16 : c.d_btable, flags_d, reinterpret_cast<uint32_t *>(fault_d), marks_d,
                                  s.stream);
     if (e == hipSuccess && !zero_copy)
       e = hipMemcpyAsync(h + flag_off, s.d_buf + flag_off, fault_off + kFaultBytes - flag_off, hipMemcpyDeviceToHost,
@@ -583,15 +588,18 @@ int committee_run(const CommitteeDev &cd, const uint32_t *key_idx, const uint8_t
 
 // Builds comb tables for `nkeys` encodings already in HBM at d_encs into
 // tables[i] (device pointers, host array), flags into d_kflags, on stream st.
-// Keys are built in runs of contiguous table memory.
+// Keys are built in runs of contiguous table memory.  digit_bits: 8, or 4 for
+// compact tables (d_tmp sized by the matching hsv_comb*_tmp_bytes(tmp_keys)).
 hipError_t build_tables(const uint8_t *d_encs, uint32_t nkeys, uint32_t *const *tables, uint8_t *d_kflags,
-                        uint32_t *d_tmp, uint32_t tmp_keys, hipStream_t st) {
-  const uint64_t words = hsv_comb_table_bytes() / 4;
+                        uint32_t *d_tmp, uint32_t tmp_keys, hipStream_t st, int digit_bits = 8) {
+  const bool compact = digit_bits == 4;
+  const uint64_t words = (compact ? hsv_comb4_table_bytes() : hsv_comb_table_bytes()) / 4;
   uint32_t i = 0;
   while (i < nkeys) {
     uint32_t j = i + 1;
     while (j < nkeys && j - i < tmp_keys && tables[j] == tables[j - 1] + words) ++j;
-    const hipError_t e = hsv_launch_comb_build(d_encs + (size_t)i * 32, j - i, 1, tables[i], d_tmp, d_kflags + i, st);
+    const hipError_t e = (compact ? hsv_launch_comb4_build : hsv_launch_comb_build)(d_encs + (size_t)i * 32, j - i, 1,
+                                                                                    tables[i], d_tmp, d_kflags + i, st);
     if (e != hipSuccess) return e;
     i = j;
   }
@@ -621,8 +629,22 @@ struct hsv_committee {
 extern "C" {
 
 int hsv_committee_create(const uint8_t *pks, size_t n, hsv_committee **out) {
+  return hsv_committee_create_ex(pks, n, HSV_COMMITTEE_DIGITS_FULL, out);
+}
+
+int hsv_committee_digit_bits(const hsv_committee *cm) { return cm ? cm->dev.digit_bits : 0; }
+
+uint64_t hsv_committee_table_bytes(const hsv_committee *cm) {
+  if (!cm) return 0;
+  return (uint64_t)cm->dev.n * (cm->dev.digit_bits == 4 ? hsv_comb4_table_bytes() : hsv_comb_table_bytes());
+}
+
+int hsv_committee_create_ex(const uint8_t *pks, size_t n, int digit_bits, hsv_committee **out) {
   if (!out || (!pks && n)) return fail(HSV_ERR_INVALID_ARG, "null argument");
   if (n > (1u << 20)) return fail(HSV_ERR_INVALID_ARG, "committee too large");
+  if (digit_bits != HSV_COMMITTEE_DIGITS_FULL && digit_bits != HSV_COMMITTEE_DIGITS_COMPACT)
+    return fail(HSV_ERR_INVALID_ARG, "digit_bits must be 8 or 4");
+  const bool compact = digit_bits == HSV_COMMITTEE_DIGITS_COMPACT;
   int rc = ensure_init();
   if (rc != HSV_OK) return rc;
   const int dev = home_device();
@@ -633,11 +655,14 @@ int hsv_committee_create(const uint8_t *pks, size_t n, hsv_committee **out) {
   std::unique_ptr<hsv_committee> cm(new hsv_committee());
   cm->dev.device = dev;
   cm->dev.n = (uint32_t)n;
+  cm->dev.digit_bits = digit_bits;
   cm->h_pks.assign(pks, pks + 32 * n);
   cm->dev.h_pks = cm->h_pks.data();
   for (size_t i = 0; i < n; ++i) cm->index.emplace(key_of(pks + 32 * i), (uint32_t)i);
   if (n) {
-    const uint64_t words = hsv_comb_table_bytes() / 4;
+    const uint64_t table_bytes = compact ? hsv_comb4_table_bytes() : hsv_comb_table_bytes();
+    const uint64_t words = table_bytes / 4;
+    const uint32_t run_keys = std::min<uint32_t>((uint32_t)n, 1024);  // keys per build launch
     uint32_t *d_tmp = nullptr;
     hipStream_t st = nullptr;
     std::vector<uint32_t *> ptrs(n);
@@ -646,9 +671,9 @@ int hsv_committee_create(const uint8_t *pks, size_t n, hsv_committee **out) {
     hipError_t e = hipMalloc(&cm->d_pks, n * 32);
     if (e == hipSuccess) e = hipMalloc(&cm->d_keytab, keytab.size() * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMalloc(&cm->d_kflags, n);
-    if (e == hipSuccess) e = hipMalloc(&cm->d_tables, n * hsv_comb_table_bytes());
+    if (e == hipSuccess) e = hipMalloc(&cm->d_tables, n * table_bytes);
     if (e == hipSuccess) e = hipMalloc(&cm->d_tabptr, n * sizeof(uint32_t *));
-    if (e == hipSuccess) e = hipMalloc(&d_tmp, hsv_comb_tmp_bytes(std::min<uint32_t>((uint32_t)n, 1024)));
+    if (e == hipSuccess) e = hipMalloc(&d_tmp, compact ? hsv_comb4_tmp_bytes(run_keys) : hsv_comb_tmp_bytes(run_keys));
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
     for (size_t i = 0; e == hipSuccess && i < n; ++i) ptrs[i] = cm->d_tables + i * words;
     if (e == hipSuccess) e = hipMemcpyAsync(cm->d_pks, pks, n * 32, hipMemcpyHostToDevice, st);
@@ -657,7 +682,7 @@ int hsv_committee_create(const uint8_t *pks, size_t n, hsv_committee **out) {
     if (e == hipSuccess)
       e = hipMemcpyAsync(cm->d_keytab, keytab.data(), keytab.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
     if (e == hipSuccess)
-      e = build_tables(cm->d_pks, (uint32_t)n, ptrs.data(), cm->d_kflags, d_tmp, std::min<uint32_t>((uint32_t)n, 1024), st);
+      e = build_tables(cm->d_pks, (uint32_t)n, ptrs.data(), cm->d_kflags, d_tmp, run_keys, st, digit_bits);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (st) (void)hipStreamDestroy(st);
     if (d_tmp) {
@@ -705,10 +730,12 @@ int hsv_committee_verify_device(const hsv_committee *cm, const uint32_t *d_key_i
   if (sig_stride < 64 || (msg_stride != 0 && msg_stride < 32)) return fail(HSV_ERR_INVALID_ARG, "record strides overlap");
   if (m > 0xffffffffu) return fail(HSV_ERR_INVALID_ARG, "batch too large");
   DeviceCall call;
-  const int rc = call.begin(d_sig, stream, d_fault, DeviceCall::kNarrow, "committee", cm->dev.device);
+  const bool compact = cm->dev.digit_bits == 4;  // its kernel reads the wide comb of B
+  const int rc = call.begin(d_sig, stream, d_fault, compact ? DeviceCall::kWide : DeviceCall::kNarrow, "committee",
+                            cm->dev.device);
   if (rc != HSV_OK) return rc;
   const hipError_t e = hsv_launch_comb_verify(d_key_idx, d_sig, sig_stride, d_msg, msg_stride, (uint32_t)m, cm->dev.d_pks,
-                                              cm->dev.d_kflags, cm->dev.n, cm->dev.d_tabptr, call.comb, d_flags,
+                                              cm->dev.d_kflags, cm->dev.n, cm->dev.d_tabptr, cm->dev.digit_bits, call.comb, d_flags,
                                               call.fault, nullptr, call.stream);
   return e == hipSuccess ? HSV_OK : hip_fail("committee verify launch", e);
 }
@@ -805,8 +832,8 @@ int committee_tx_enqueue(const hsv_committee &cm, const uint32_t *btable, const 
     const size_t m = std::min(kChunk, n - base);
     const hipError_t e = hsv_launch_committee_tx(
         d_offsets ? d_txs : d_txs + base * tx_size, d_offsets ? d_offsets + base : nullptr, tx_size, (uint32_t)m,
-        cm.d_keytab, cm.keymask, KeyHash::seed(), cm.dev.d_pks, cm.dev.d_kflags, cm.dev.n, cm.dev.d_tabptr, btable,
-        comb16, d_flags ? d_flags + base : nullptr, d_bits ? d_bits + base / 32 : nullptr, d_fault, d_totals, s);
+        cm.d_keytab, cm.keymask, KeyHash::seed(), cm.dev.d_pks, cm.dev.d_kflags, cm.dev.n, cm.dev.d_tabptr,
+        cm.dev.digit_bits, btable, comb16, d_flags ? d_flags + base : nullptr, d_bits ? d_bits + base / 32 : nullptr, d_fault, d_totals, s);
     if (e != hipSuccess) return hip_fail("committee transaction launch", e);
   }
   return HSV_OK;
@@ -898,8 +925,8 @@ int committee_msgs_enqueue(const hsv_committee &cm, const uint32_t *btable, cons
         d_pk + base * pk_stride, pk_stride, d_sig + base * sig_stride, sig_stride,
         d_offsets ? d_msgs : d_msgs + base * msg_stride, d_offsets ? d_offsets + base : nullptr, msg_len, msg_stride,
         (uint32_t)m, cm.d_keytab, cm.keymask, KeyHash::seed(), cm.dev.d_pks, cm.dev.d_kflags, cm.dev.n,
-        cm.dev.d_tabptr, btable, comb16, d_flags ? d_flags + base : nullptr, d_bits ? d_bits + base / 32 : nullptr,
-        d_fault, d_totals, s);
+        cm.dev.d_tabptr, cm.dev.digit_bits, btable, comb16, d_flags ? d_flags + base : nullptr,
+        d_bits ? d_bits + base / 32 : nullptr, d_fault, d_totals, s);
     if (e != hipSuccess) return hip_fail("committee message launch", e);
   }
   return HSV_OK;
@@ -948,7 +975,7 @@ int committee_msgs_host(const hsv_committee &cm, const uint8_t *pk, const uint8_
           blk.at(off_pk), 32, blk.at(off_sig), 64, blk.at(off_msg),
           offsets ? reinterpret_cast<uint64_t *>(blk.at(off_offs)) : nullptr, msg_len, msg_stride, (uint32_t)m,
           cm.d_keytab, cm.keymask, KeyHash::seed(), cm.dev.d_pks, cm.dev.d_kflags, cm.dev.n, cm.dev.d_tabptr,
-          c.d_btable, c.d_btable16, blk.at(off_flags), nullptr, blk.fault(), d_totals, st));
+          cm.dev.digit_bits, c.d_btable, c.d_btable16, blk.at(off_flags), nullptr, blk.fault(), d_totals, st));
     blk.out(flags_out + a, off_flags, m);
     rc = blk.finish("hsv_committee_verify_msgs");
     if (rc != HSV_OK) return rc;

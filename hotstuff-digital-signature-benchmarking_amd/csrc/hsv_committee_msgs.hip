@@ -150,6 +150,43 @@ hsv_cmsg_comb_kernel(const uint8_t *__restrict__ sig, uint64_t sig_stride, uint3
   report_faults(fault, bad);
 }
 
+// hsv_cmsg_comb_kernel for a committee with compact (4-bit digit) tables
+// (verify_one_comb4_k: 80 mixed additions and one decompression; comb16: the
+// wide comb of B, where hsv_cmsg_comb_kernel reads the narrow one): the same
+// dealing from hit_next, the same redone first entry past the list's end, the
+// same stores.
+__global__ void __launch_bounds__(256, 2)
+hsv_cmsg_comb4_kernel(const uint8_t *__restrict__ sig, uint64_t sig_stride, uint32_t n, CmsgCounters *__restrict__ ctr,
+                      const uint2 *__restrict__ hit_list, const uint32_t *__restrict__ krec,
+                      const uint8_t *__restrict__ key_flags, uint32_t nkeys,
+                      const uint32_t *const *__restrict__ key_tables, const uint32_t *__restrict__ comb16,
+                      uint8_t *__restrict__ flags_out, uint32_t *__restrict__ strict_bits, uint32_t inject,
+                      uint32_t *__restrict__ fault) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t nh = min((uint32_t)__builtin_amdgcn_readfirstlane(ctr->hits), n);
+  uint32_t bad = 0;
+  for (;;) {
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(&ctr->hit_next, 64u);
+    base = __builtin_amdgcn_readfirstlane(__shfl(base, 0));
+    if (base >= nh) break;
+    const uint32_t j = base + lane;
+    const uint2 e = hit_list[j < nh ? j : base];
+    const uint32_t i = min(e.x, n - 1u), kk = e.y < nkeys ? e.y : 0u;  // (the route kernel wrote both in range)
+    uint32_t sigw[16];
+    load_words8(sig + (uint64_t)i * sig_stride, sigw);
+    load_words8(sig + (uint64_t)i * sig_stride + 32, sigw + 8);
+    sc k;
+    HSV_UNROLL
+    for (int w = 0; w < 8; ++w) k.v[w] = krec[(uint64_t)w * n + i];
+    const uint32_t f = verify_one_comb4_k(key_flags[kk], sigw, k, key_tables[kk], comb16, inject);
+    bad |= (f & kFault) ? 1u : 0u;
+    if (flags_out) flags_out[i] = (uint8_t)f;
+    if (strict_bits && (f & kStrictOk)) atomicOr(&strict_bits[i >> 5], 1u << (i & 31u));
+  }
+  report_faults(fault, bad);
+}
+
 // hsv_ctx_generic_kernel (hsv_mempool.hip) with pk, R and s read in place from
 // the caller's arrays at their strides instead of 128-byte records, and the
 // fallback items' k mod l read from the b words of their prepass record, as
@@ -231,6 +268,7 @@ namespace {
 // blocks per CU of the two persistent passes and the device's CUs, cached per device
 struct CmsgGrids {
   int comb_bpc, generic_bpc, cus;
+  int comb4_bpc;  // the compact comb pass, from its own occupancy query
 };
 hipError_t cmsg_grids(int dev, CmsgGrids *out) {
   static std::mutex mu;
@@ -238,15 +276,18 @@ hipError_t cmsg_grids(int dev, CmsgGrids *out) {
   std::lock_guard<std::mutex> lk(mu);
   auto it = per_dev.find(dev);
   if (it == per_dev.end()) {
-    int bc = 0, bg = 0, cus = 0;
+    int bc = 0, bc4 = 0, bg = 0, cus = 0;
     hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
         &bc, reinterpret_cast<const void *>(hsv::hsv_cmsg_comb_kernel), 256, 0);
+    if (e == hipSuccess)
+      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+          &bc4, reinterpret_cast<const void *>(hsv::hsv_cmsg_comb4_kernel), 256, 0);
     if (e == hipSuccess)
       e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
           &bg, reinterpret_cast<const void *>(hsv::hsv_cmsg_generic_kernel<4, HSV_HP_WAVES, 16>), hsv::kBlock, 0);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (e != hipSuccess) return e;
-    it = per_dev.emplace(dev, CmsgGrids{std::max(1, bc), std::max(1, bg), std::max(1, cus)}).first;
+    it = per_dev.emplace(dev, CmsgGrids{std::max(1, bc), std::max(1, bg), std::max(1, cus), std::max(1, bc4)}).first;
   }
   *out = it->second;
   return hipSuccess;
@@ -267,11 +308,12 @@ extern "C" hipError_t hsv_launch_committee_msgs(const uint8_t *pk, uint64_t pk_s
                                                 uint64_t msg_len, uint64_t msg_stride, uint32_t n,
                                                 const uint32_t *keytab, uint32_t keymask, uint64_t seed,
                                                 const uint8_t *pks, const uint8_t *key_flags, uint32_t nkeys,
-                                                const uint32_t *const *key_tables, const uint32_t *btable,
-                                                const uint32_t *comb16, uint8_t *flags_out, uint32_t *strict_bits,
-                                                uint32_t *fault, uint64_t *totals, hipStream_t stream) {
+                                                const uint32_t *const *key_tables, int digit_bits,
+                                                const uint32_t *btable, const uint32_t *comb16, uint8_t *flags_out,
+                                                uint32_t *strict_bits, uint32_t *fault, uint64_t *totals,
+                                                hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  if (n > (1u << 22) || !pk || !sig || !btable || !comb16 || !fault ||
+  if (n > (1u << 22) || (digit_bits != 8 && digit_bits != 4) || !pk || !sig || !btable || !comb16 || !fault ||
       (nkeys && (!keytab || !pks || !key_flags || !key_tables)))
     return hipErrorInvalidValue;
   int dev = 0;
@@ -282,7 +324,8 @@ extern "C" hipError_t hsv_launch_committee_msgs(const uint8_t *pk, uint64_t pk_s
   if (e != hipSuccess) return e;
   const int cus = hsvi_resident_started() && g.cus > 1 ? g.cus - 1 : g.cus;
   const uint32_t blocks_needed = (n + hsv::kBlock - 1) / hsv::kBlock;
-  const uint32_t grid_c = std::min<uint32_t>(blocks_needed, (uint32_t)(g.comb_bpc * cus));
+  const uint32_t grid_c =
+      std::min<uint32_t>(blocks_needed, (uint32_t)((digit_bits == 4 ? g.comb4_bpc : g.comb_bpc) * cus));
   const uint32_t grid_g = std::min<uint32_t>(blocks_needed, (uint32_t)(g.generic_bpc * cus));
   const size_t vt_bytes = (size_t)grid_g * hsv::kBlock * hsv::vt_lane_uint4<4>() * sizeof(uint4);
   const size_t canary_bytes = up256((size_t)grid_g * hsv::kBlock * sizeof(uint32_t));
@@ -311,9 +354,13 @@ extern "C" hipError_t hsv_launch_committee_msgs(const uint8_t *pk, uint64_t pk_s
                        hsvi_lattice_bits(), flags_out);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(hsv::hsv_cmsg_comb_kernel, dim3(grid_c), dim3(256), 0, stream, sig, sig_stride, n, ctr, hit_list,
-                       krec, key_flags, nkeys, key_tables, btable, flags_out, strict_bits, inject, fault);
+  if (e == hipSuccess) {  // the committee's table width decides the comb pass, nothing else
+    if (digit_bits == 4)
+      hipLaunchKernelGGL(hsv::hsv_cmsg_comb4_kernel, dim3(grid_c), dim3(256), 0, stream, sig, sig_stride, n, ctr,
+                         hit_list, krec, key_flags, nkeys, key_tables, comb16, flags_out, strict_bits, inject, fault);
+    else
+      hipLaunchKernelGGL(hsv::hsv_cmsg_comb_kernel, dim3(grid_c), dim3(256), 0, stream, sig, sig_stride, n, ctr, hit_list,
+                         krec, key_flags, nkeys, key_tables, btable, flags_out, strict_bits, inject, fault);
     e = hipGetLastError();
   }
   if (e == hipSuccess) {

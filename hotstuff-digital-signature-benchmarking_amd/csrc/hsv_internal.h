@@ -161,18 +161,26 @@ hipError_t hsv_launch_comb_resident(QcResidentReq *d_req, uint64_t idle_ticks, h
 uint32_t hsv_comb_resident_votes(void);  // votes one request may hold (0: no service in this build)
 hipError_t hsv_launch_comb_build(const uint8_t *encs, uint32_t nkeys, uint32_t negate, uint32_t *tables,
                                  uint32_t *tmp, uint8_t *key_flags, hipStream_t stream);
-// key_tables[i]: device pointer to key i's comb table (hsv_comb_table_bytes)
+// key_tables[i]: device pointer to key i's comb table; digit_bits: 8
+// (hsv_comb_table_bytes each; btable: the narrow comb of B) or 4 (compact,
+// hsv_comb4_table_bytes each: the one-lane kernel at every m, done must be
+// NULL, and btable is the WIDE comb of B, hsv_comb16_table_bytes)
 hipError_t hsv_launch_comb_verify(const uint32_t *key_idx, const uint8_t *sig, uint64_t sig_stride,
                                   const uint8_t *msg, uint64_t msg_stride, uint32_t m, const uint8_t *pks,
                                   const uint8_t *key_flags, uint32_t nkeys, const uint32_t *const *key_tables,
-                                  const uint32_t *btable, uint8_t *flags_out, uint32_t *fault, uint32_t *done,
-                                  hipStream_t stream);
+                                  int digit_bits, const uint32_t *btable, uint8_t *flags_out, uint32_t *fault,
+                                  uint32_t *done, hipStream_t stream);
 // Completion markers of the latency form (done != NULL above, m votes): one
 // word per block, set to 1 by the block once its flags are released to the
 // system; 0 when m is above the latency form's range (no markers).
 uint32_t hsv_comb_marker_blocks(uint32_t m);
 uint64_t hsv_comb_table_bytes(void);
 uint64_t hsv_comb_tmp_bytes(uint32_t nkeys);
+// compact (4-bit digit) key tables, hsv_comb.hpp: nkeys tables contiguous at `tables`
+hipError_t hsv_launch_comb4_build(const uint8_t *encs, uint32_t nkeys, uint32_t negate, uint32_t *tables,
+                                  uint32_t *tmp, uint8_t *key_flags, hipStream_t stream);
+uint64_t hsv_comb4_table_bytes(void);
+uint64_t hsv_comb4_tmp_bytes(uint32_t nkeys);
 // wide (16-bit digit) comb table of B, hsv_comb.hpp
 hipError_t hsv_launch_comb16_build(uint32_t *table, uint32_t *tmp, hipStream_t stream);
 uint64_t hsv_comb16_table_bytes(void);
@@ -217,7 +225,9 @@ hipError_t hsv_launch_verify_tx(int variant, const uint8_t *txs, const uint64_t 
 // kernel (records, key lookup in keytab / keymask / seed over the committee's
 // pks, hit and miss lists, the misses' prepass), the comb pass over the hit
 // list (key_flags, key_tables, btable: the narrow comb of B) and the generic
-// pass over the miss list (comb16: the wide comb).  Every flag byte and strict
+// pass over the miss list (comb16: the wide comb); digit_bits (8 or 4): the
+// width of key_tables, which picks the comb pass (the compact one reads comb16
+// for [s]B, not btable).  Every flag byte and strict
 // word of the round is written; fault as hsv_launch_verify.  totals (may be
 // NULL): three 64-bit device words that receive += {hits, misses, fallback
 // items}.  nkeys == 0: every transaction is a miss, the committee arrays may
@@ -225,7 +235,7 @@ hipError_t hsv_launch_verify_tx(int variant, const uint8_t *txs, const uint64_t 
 hipError_t hsv_launch_committee_tx(const uint8_t *txs, const uint64_t *offsets, uint64_t tx_size, uint32_t n,
                                    const uint32_t *keytab, uint32_t keymask, uint64_t seed, const uint8_t *pks,
                                    const uint8_t *key_flags, uint32_t nkeys, const uint32_t *const *key_tables,
-                                   const uint32_t *btable, const uint32_t *comb16, uint8_t *flags_out,
+                                   int digit_bits, const uint32_t *btable, const uint32_t *comb16, uint8_t *flags_out,
                                    uint32_t *strict_bits, uint32_t *fault, uint64_t *totals, hipStream_t stream);
 // Ed25519 over messages of any length (hsv_verify_msgs*): k = SHA-512(R || A
 // || M) over the whole message.  Message i is msgs[offsets[i], offsets[i+1])
@@ -266,7 +276,7 @@ hipError_t hsv_launch_committee_msgs(const uint8_t *pk, uint64_t pk_stride, cons
                                      const uint8_t *msgs, const uint64_t *offsets, uint64_t msg_len,
                                      uint64_t msg_stride, uint32_t n, const uint32_t *keytab, uint32_t keymask,
                                      uint64_t seed, const uint8_t *pks, const uint8_t *key_flags, uint32_t nkeys,
-                                     const uint32_t *const *key_tables, const uint32_t *btable,
+                                     const uint32_t *const *key_tables, int digit_bits, const uint32_t *btable,
                                      const uint32_t *comb16, uint8_t *flags_out, uint32_t *strict_bits,
                                      uint32_t *fault, uint64_t *totals, hipStream_t stream);
 // flags 0 (and STRICT_OK bit cleared) for transactions shorter than 96 bytes

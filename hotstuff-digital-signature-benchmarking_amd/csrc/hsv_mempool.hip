@@ -463,6 +463,42 @@ hsv_ctx_comb_kernel(const uint8_t *__restrict__ records, uint32_t n, CtxCounters
   report_faults(fault, bad);
 }
 
+// hsv_ctx_comb_kernel for a committee with compact (4-bit digit) tables
+// (verify_one_comb4: 80 mixed additions and one decompression; comb16: the
+// wide comb of B, where hsv_ctx_comb_kernel reads the narrow one): the same
+// dealing from hit_next, the same redone first entry past the list's end, the
+// same stores.
+__global__ void __launch_bounds__(256, 2)
+hsv_ctx_comb4_kernel(const uint8_t *__restrict__ records, uint32_t n, CtxCounters *__restrict__ ctr,
+                     const uint2 *__restrict__ hit_list, const uint8_t *__restrict__ pks,
+                     const uint8_t *__restrict__ key_flags, uint32_t nkeys,
+                     const uint32_t *const *__restrict__ key_tables, const uint32_t *__restrict__ comb16,
+                     uint8_t *__restrict__ flags_out, uint32_t *__restrict__ strict_bits, uint32_t inject,
+                     uint32_t *__restrict__ fault) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t nh = min((uint32_t)__builtin_amdgcn_readfirstlane(ctr->hits), n);
+  uint32_t bad = 0;
+  for (;;) {
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(&ctr->hit_next, 64u);
+    base = __builtin_amdgcn_readfirstlane(__shfl(base, 0));
+    if (base >= nh) break;
+    const uint32_t j = base + lane;
+    const uint2 e = hit_list[j < nh ? j : base];
+    const uint32_t i = min(e.x, n - 1u), kk = e.y < nkeys ? e.y : 0u;  // (the route kernel wrote both in range)
+    uint32_t pkw[8], sigw[16], msgw[8];
+    {  // the member's key bytes (the record's are equal), R || s and the digest from the record
+      const uint8_t *t = records + (uint64_t)i * 128u;
+      load_triple(pks + (uint64_t)kk * 32u, 0, t + 32, 0, t + 96, 0, 0, pkw, sigw, msgw);
+    }
+    const uint32_t f = verify_one_comb4(pkw, key_flags[kk], sigw, msgw, key_tables[kk], comb16, inject);
+    bad |= (f & kFault) ? 1u : 0u;
+    if (flags_out) flags_out[i] = (uint8_t)f;
+    if (strict_bits && (f & kStrictOk)) atomicOr(&strict_bits[i >> 5], 1u << (i & 31u));
+  }
+  report_faults(fault, bad);
+}
+
 // hsv_verify_hp_kernel over the miss list: the fallback list first (the
 // full-length path), then 64 miss-list entries per batch through
 // verify_one_prepped; pk / R (fallback items: s and the digest too) from the
@@ -604,6 +640,7 @@ namespace {
 // blocks per CU of the two persistent passes and the device's CUs, cached per device
 struct CtxGrids {
   int comb_bpc, generic_bpc, cus;
+  int comb4_bpc;  // the compact comb pass, from its own occupancy query
 };
 hipError_t ctx_grids(int dev, CtxGrids *out) {
   static std::mutex mu;
@@ -611,15 +648,18 @@ hipError_t ctx_grids(int dev, CtxGrids *out) {
   std::lock_guard<std::mutex> lk(mu);
   auto it = per_dev.find(dev);
   if (it == per_dev.end()) {
-    int bc = 0, bg = 0, cus = 0;
+    int bc = 0, bc4 = 0, bg = 0, cus = 0;
     hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
         &bc, reinterpret_cast<const void *>(hsv::hsv_ctx_comb_kernel), 256, 0);
+    if (e == hipSuccess)
+      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+          &bc4, reinterpret_cast<const void *>(hsv::hsv_ctx_comb4_kernel), 256, 0);
     if (e == hipSuccess)
       e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
           &bg, reinterpret_cast<const void *>(hsv::hsv_ctx_generic_kernel<4, HSV_HP_WAVES, 16>), hsv::kBlock, 0);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (e != hipSuccess) return e;
-    it = per_dev.emplace(dev, CtxGrids{std::max(1, bc), std::max(1, bg), std::max(1, cus)}).first;
+    it = per_dev.emplace(dev, CtxGrids{std::max(1, bc), std::max(1, bg), std::max(1, cus), std::max(1, bc4)}).first;
   }
   *out = it->second;
   return hipSuccess;
@@ -637,11 +677,12 @@ size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 extern "C" hipError_t hsv_launch_committee_tx(const uint8_t *txs, const uint64_t *offsets, uint64_t tx_size, uint32_t n,
                                               const uint32_t *keytab, uint32_t keymask, uint64_t seed,
                                               const uint8_t *pks, const uint8_t *key_flags, uint32_t nkeys,
-                                              const uint32_t *const *key_tables, const uint32_t *btable,
-                                              const uint32_t *comb16, uint8_t *flags_out, uint32_t *strict_bits,
-                                              uint32_t *fault, uint64_t *totals, hipStream_t stream) {
+                                              const uint32_t *const *key_tables, int digit_bits,
+                                              const uint32_t *btable, const uint32_t *comb16, uint8_t *flags_out,
+                                              uint32_t *strict_bits, uint32_t *fault, uint64_t *totals,
+                                              hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  if (n > (1u << 22) || !btable || !comb16 || !fault || (nkeys && (!keytab || !pks || !key_flags || !key_tables)))
+  if (n > (1u << 22) || (digit_bits != 8 && digit_bits != 4) || !btable || !comb16 || !fault || (nkeys && (!keytab || !pks || !key_flags || !key_tables)))
     return hipErrorInvalidValue;
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
@@ -651,7 +692,8 @@ extern "C" hipError_t hsv_launch_committee_tx(const uint8_t *txs, const uint64_t
   if (e != hipSuccess) return e;
   const int cus = hsvi_resident_started() && g.cus > 1 ? g.cus - 1 : g.cus;
   const uint32_t blocks_needed = (n + hsv::kBlock - 1) / hsv::kBlock;
-  const uint32_t grid_c = std::min<uint32_t>(blocks_needed, (uint32_t)(g.comb_bpc * cus));
+  const uint32_t grid_c =
+      std::min<uint32_t>(blocks_needed, (uint32_t)((digit_bits == 4 ? g.comb4_bpc : g.comb_bpc) * cus));
   const uint32_t grid_g = std::min<uint32_t>(blocks_needed, (uint32_t)(g.generic_bpc * cus));
   const size_t vt_bytes = (size_t)grid_g * hsv::kBlock * hsv::vt_lane_uint4<4>() * sizeof(uint4);
   const size_t canary_bytes = up256((size_t)grid_g * hsv::kBlock * sizeof(uint32_t));
@@ -679,9 +721,13 @@ extern "C" hipError_t hsv_launch_committee_tx(const uint8_t *txs, const uint64_t
                        miss_list, prep, fb_list, hsvi_lattice_bits(), flags_out);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(hsv::hsv_ctx_comb_kernel, dim3(grid_c), dim3(256), 0, stream, records, n, ctr, hit_list, pks,
-                       key_flags, nkeys, key_tables, btable, flags_out, strict_bits, inject, fault);
+  if (e == hipSuccess) {  // the committee's table width decides the comb pass, nothing else
+    if (digit_bits == 4)
+      hipLaunchKernelGGL(hsv::hsv_ctx_comb4_kernel, dim3(grid_c), dim3(256), 0, stream, records, n, ctr, hit_list, pks,
+                         key_flags, nkeys, key_tables, comb16, flags_out, strict_bits, inject, fault);
+    else
+      hipLaunchKernelGGL(hsv::hsv_ctx_comb_kernel, dim3(grid_c), dim3(256), 0, stream, records, n, ctr, hit_list, pks,
+                         key_flags, nkeys, key_tables, btable, flags_out, strict_bits, inject, fault);
     e = hipGetLastError();
   }
   if (e == hipSuccess) {

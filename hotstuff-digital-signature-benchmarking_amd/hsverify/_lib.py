@@ -114,6 +114,9 @@ def _declare(lib):
         "hsv_sign_many": (ctypes.c_int, [c_u8p, c_u8p, sz, sz, c_u8p, c_u8p, ctypes.c_int]),
         "hsv_measure_mad_peak": (ctypes.c_double, []),
         "hsv_committee_create": (ctypes.c_int, [c_u8p, sz, ctypes.POINTER(ctypes.c_void_p)]),
+        "hsv_committee_create_ex": (ctypes.c_int, [c_u8p, sz, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+        "hsv_committee_digit_bits": (ctypes.c_int, [ctypes.c_void_p]),
+        "hsv_committee_table_bytes": (ctypes.c_uint64, [ctypes.c_void_p]),
         "hsv_committee_destroy": (None, [ctypes.c_void_p]),
         "hsv_committee_size": (sz, [ctypes.c_void_p]),
         "hsv_committee_index": (ctypes.c_int64, [ctypes.c_void_p, c_u8p]),

@@ -109,7 +109,7 @@ HSV_API const char *hsv_last_error(void);
  * hsv_verify_transactions_device) take the optional d_fault argument before
  * `stream`; a caller built against 0.2.x headers must be rebuilt (check
  * HSV_ABI_VERSION against hsv_abi_version() at startup).  Entry points added
- * since (the last: hsv_committee_verify_msgs*) change no existing signature
+ * since (the last: hsv_committee_create_ex) change no existing signature
  * and leave both the version and HSV_ABI_VERSION as they are. */
 #define HSV_ABI_VERSION 3
 HSV_API const char *hsv_version(void);
@@ -261,6 +261,37 @@ HSV_API int hsv_device_faults(int device, int clear);
 typedef struct hsv_committee hsv_committee;
 /* Build tables for n public keys (n*32 B). */
 HSV_API int hsv_committee_create(const uint8_t *pks, size_t n, hsv_committee **out);
+/* The same with the table width chosen: digit_bits 8 (hsv_committee_create's
+ * tables: 32 positions x 128 entries, 384 KiB per key) or 4 (compact: 64
+ * positions x 8 entries, 48 KiB per key, so 2^20 keys take 48 GiB instead of
+ * 384 GiB and 100 000 keys 4.6 GiB instead of 36.6 GiB); any other value is
+ * HSV_ERR_INVALID_ARG.  A compact committee is accepted by every call that
+ * takes an hsv_committee, with the flags, strict bits, fault words, chunking,
+ * alignment rules and error codes of a full one over the same keys; it pays
+ * 80 mixed additions per signature instead of 64.  It has no latency form:
+ * every batch size runs one item per lane -- no zero-copy form, no
+ * 16-lanes-per-vote kernel, no resident service -- so small batches (a QC)
+ * belong to a full committee.  Both kinds may exist side by side, over the
+ * same keys or different ones.
+ * When to use it (profiles/committee_compact_bench_2p20.json: 2^20
+ * device-resident items, a uniformly random member per item, every ratio
+ * within one run): with every signer a member a compact committee runs at
+ * 2.22 - 2.31 x the rate of the generic call (hsv_verify_msgs_device on
+ * 32-byte messages, hsv_verify_transactions_device on 512-byte transactions)
+ * at K = 1000, 1.98 - 2.02 x at 2^14 and 1.65 - 1.71 x at 2^17 keys (6 GiB of
+ * tables, far beyond the Infinity Cache: 0.71 - 0.74 of its own rate at K =
+ * 1000), and at 0.89 - 0.91 x the rate of a full committee at K = 1000; with
+ * half of the signers members it takes 0.75 - 0.82 of the generic call's
+ * time.  Use it where the full tables do not fit; where they do, the full
+ * committee is faster and has the latency forms.  2^17 keys build in 0.18 -
+ * 0.36 s. */
+#define HSV_COMMITTEE_DIGITS_FULL 8    /* 384 KiB per key */
+#define HSV_COMMITTEE_DIGITS_COMPACT 4 /* 48 KiB per key */
+HSV_API int hsv_committee_create_ex(const uint8_t *pks, size_t n, int digit_bits, hsv_committee **out);
+/* 8 or 4; 0 for NULL. */
+HSV_API int hsv_committee_digit_bits(const hsv_committee *c);
+/* Table memory the committee holds on its device: n * 393216 or n * 49152. */
+HSV_API uint64_t hsv_committee_table_bytes(const hsv_committee *c);
 HSV_API void hsv_committee_destroy(hsv_committee *c);
 HSV_API size_t hsv_committee_size(const hsv_committee *c);
 /* Index of pk in the committee, or -1. */
