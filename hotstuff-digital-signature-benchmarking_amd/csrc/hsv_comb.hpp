@@ -31,26 +31,24 @@ constexpr uint64_t kCombTableWords = (uint64_t)kCombPos * kCombEnt * kCombEntryW
 // key flag byte stored next to each committee key
 enum : uint32_t { kKeyAOk = 0x1, kKeySmallA = 0x2 };
 
-// Fill entries m = 1..128 of one position from base = [2^(8j)]P:
-// out[(m-1)*24 ...] = affine Niels of [m]base.  tmp: 128 * 8 words scratch
-// (prefix products of Z for one batched inversion).
-HSV_INL void comb_build_position(const ge_ext &base, uint32_t *out, uint32_t *tmp) {
-  const ge_cached bc = ge_to_cached(base);
-  ge_ext acc = base;
-  fe pp = fe_small(1);
+// The two halves of a table build, shared by the three builders below (each
+// keeps its own start and step rule).  First every entry is stored projective,
+// X, Y, Z at e, and the running product pp of the Zs so far at t (8 words of
+// the lane's scratch per entry) ...
+HSV_INL void comb_store_projective(const ge_ext &acc, fe &pp, uint32_t *e, uint32_t *t) {
+  fe_pack(acc.X, e);
+  fe_pack(acc.Y, e + 8);
+  fe_pack(acc.Z, e + 16);
+  pp = fe_mul(pp, acc.Z);
+  fe_pack(pp, t);
+}
+
+// ... then one batched inversion of pp = Z_1 ... Z_count turns the `count`
+// entries at out into affine Niels words, last entry first.
+HSV_INL void comb_normalise(uint32_t *out, const uint32_t *tmp, const fe &pp, int count) {
+  fe inv = fe_invert(pp);
   HSV_NOUNROLL
-  for (int m = 1; m <= kCombEnt; ++m) {
-    if (m > 1) acc = ge_add_cached<true>(acc, bc);
-    uint32_t *e = out + (m - 1) * kCombEntryWords;
-    fe_pack(acc.X, e);
-    fe_pack(acc.Y, e + 8);
-    fe_pack(acc.Z, e + 16);
-    pp = fe_mul(pp, acc.Z);
-    fe_pack(pp, tmp + (m - 1) * 8);
-  }
-  fe inv = fe_invert(pp);  // 1 / (Z_1 ... Z_128)
-  HSV_NOUNROLL
-  for (int m = kCombEnt; m >= 1; --m) {
+  for (int m = count; m >= 1; --m) {
     uint32_t *e = out + (m - 1) * kCombEntryWords;
     const fe X = fe_from_words_masked(e), Y = fe_from_words_masked(e + 8), Z = fe_from_words_masked(e + 16);
     fe zinv = inv;
@@ -63,6 +61,21 @@ HSV_INL void comb_build_position(const ge_ext &base, uint32_t *out, uint32_t *tm
     fe_pack(fe_sub(y, x), e + 8);
     fe_pack(fe_mul(fe_mul(x, y), fe_d2()), e + 16);
   }
+}
+
+// Fill entries m = 1..128 of one position from base = [2^(8j)]P:
+// out[(m-1)*24 ...] = affine Niels of [m]base.  tmp: 128 * 8 words scratch.
+// The first entry is base itself: the sum does not start from the identity.
+HSV_INL void comb_build_position(const ge_ext &base, uint32_t *out, uint32_t *tmp) {
+  const ge_cached bc = ge_to_cached(base);
+  ge_ext acc = base;
+  fe pp = fe_small(1);
+  HSV_NOUNROLL
+  for (int m = 1; m <= kCombEnt; ++m) {
+    if (m > 1) acc = ge_add_cached<true>(acc, bc);
+    comb_store_projective(acc, pp, out + (m - 1) * kCombEntryWords, tmp + (m - 1) * 8);
+  }
+  comb_normalise(out, tmp, pp, kCombEnt);
 }
 
 // Wide comb of B for the generic kernels: 16-bit signed digits, so [b]B for
@@ -87,28 +100,9 @@ HSV_INL void comb_build_run(const ge_ext &start, const ge_ext &base, uint32_t *o
   HSV_NOUNROLL
   for (int m = 1; m <= kComb16Chunk; ++m) {
     acc = ge_add_cached<true>(acc, bc);
-    uint32_t *e = out + (m - 1) * kCombEntryWords;
-    fe_pack(acc.X, e);
-    fe_pack(acc.Y, e + 8);
-    fe_pack(acc.Z, e + 16);
-    pp = fe_mul(pp, acc.Z);
-    fe_pack(pp, tmp + (m - 1) * 8);
+    comb_store_projective(acc, pp, out + (m - 1) * kCombEntryWords, tmp + (m - 1) * 8);
   }
-  fe inv = fe_invert(pp);
-  HSV_NOUNROLL
-  for (int m = kComb16Chunk; m >= 1; --m) {
-    uint32_t *e = out + (m - 1) * kCombEntryWords;
-    const fe X = fe_from_words_masked(e), Y = fe_from_words_masked(e + 8), Z = fe_from_words_masked(e + 16);
-    fe zinv = inv;
-    if (m > 1) {
-      zinv = fe_mul(inv, fe_from_words_masked(tmp + (m - 2) * 8));
-      inv = fe_mul(inv, Z);
-    }
-    const fe x = fe_mul(X, zinv), y = fe_mul(Y, zinv);
-    fe_pack(fe_add(y, x), e);
-    fe_pack(fe_sub(y, x), e + 8);
-    fe_pack(fe_mul(fe_mul(x, y), fe_d2()), e + 16);
-  }
+  comb_normalise(out, tmp, pp, kComb16Chunk);
 }
 
 // One chunk (position j, chunk c) of the wide B table: entries
@@ -184,43 +178,10 @@ HSV_INL ge_niels niels_injected(const ge_niels &n, uint32_t inject) {
   return r;
 }
 
-// Verification against a cached committee key.  ta: the key's table of -A,
-// tb: the table of B, pk: the key's original 32 bytes (hashed as-is),
-// key_flags: kKeyAOk / kKeySmallA computed when the table was built.
-// Returns the same flag byte as verify_one for (pk, sig, msg), plus kFault
-// (fault_bit).  inject: fault injection (tests), applied to the first key entry.
-HSV_INL uint32_t verify_one_comb(const uint32_t pk[8], uint32_t key_flags, const uint32_t sig[16],
-                                 const uint32_t msg[8], const uint32_t *ta, const uint32_t *tb,
-                                 uint32_t inject = kInjectNone) {
-  const uint32_t s_ok = sc_is_canonical(sig + 8);
-  uint32_t h[16];
-  sha512_96(sig, pk, msg, h);
-  const sc k = sc_reduce512(h);
-
-  // signed radix-2^8 digits of k and s (32 each), consumed from the bottom
-  uint32_t kr[9], sr[9];
-  recode_add<9, 8, kCombPos>(k.v, 8, kr);
-  recode_add<9, 8, kCombPos>(sig + 8, 8, sr);
-
-  ge_ext q = ge_identity();
-  HSV_NOUNROLL
-  for (int j = 0; j < kCombPos; ++j) {
-    const uint32_t ca = kr[0] & 0xffu, cb = sr[0] & 0xffu;
-    HSV_UNROLL
-    for (int i = 0; i < 8; ++i) {
-      kr[i] = (kr[i] >> 8) | (kr[i + 1] << 24);
-      sr[i] = (sr[i] >> 8) | (sr[i + 1] << 24);
-    }
-    kr[8] >>= 8;
-    sr[8] >>= 8;
-    const CombPosTab tpa{ta + (uint64_t)j * kCombEnt * kCombEntryWords};
-    const CombPosTab tpb{tb + (uint64_t)j * kCombEnt * kCombEntryWords};
-    ge_niels na = select_niels<8>(tpa, ca);
-    if (inject != kInjectNone && j == 0) na = niels_injected(na, inject);
-    q = ge_add_niels<true>(q, na);
-    q = ge_add_niels<true>(q, select_niels<8>(tpb, cb));
-  }
-
+// The flag byte of a comb verification, once Q = [s]B - [k]A stands: R
+// decompressed and compared, the key's flags from its table build, and
+// fault_bit.  The same byte as verify_one's for the same (pk, sig, k).
+HSV_INL uint32_t comb_flags(uint32_t s_ok, uint32_t key_flags, const uint32_t sig[16], const ge_ext &q) {
   fe rx, ry;
   const uint32_t r_ok = ge_decompress(sig, rx, ry);
   const uint32_t small_r = r_ok & y_is_small_order(ry);
@@ -236,21 +197,15 @@ HSV_INL uint32_t verify_one_comb(const uint32_t pk[8], uint32_t key_flags, const
          (a_ok ? kAOk : 0u) | (r_ok ? kROk : 0u) | fault_bit(a_ok, r_ok, q);
 }
 
-// The same after the hash: k = SHA-512(R || A || M) mod l, whatever the length
-// of M (the committee message path reads it from the route kernel's record,
-// hsv_committee_msgs.hip), so no key bytes are needed.  verify_one_comb's body
-// from the recoding on, kept as a function of its own: with verify_one_comb
-// written as the hash plus a call of this one, hipcc compiled
-// hsv_comb_verify_kernel and hsv_ctx_comb_kernel to two and three instructions
-// more than before.  tests/native/comb_k_host.cpp holds the two
-// to the same byte.
-HSV_INL uint32_t verify_one_comb_k(uint32_t key_flags, const uint32_t sig[16], const sc &k, const uint32_t *ta,
-                                   const uint32_t *tb, uint32_t inject = kInjectNone) {
-  const uint32_t s_ok = sc_is_canonical(sig + 8);
+// [s]B + [k](-A) from the full-width tables: the signed radix-2^8 digits of k
+// and s (32 each), consumed from the bottom, one entry of the key's table and
+// one of B's per position.  (The recoding sits in here: handed in as recoded
+// arrays, hsv_comb_verify_kernel came out 10 instructions shorter, not the same.)
+HSV_INL ge_ext comb_walk8(const uint32_t k[8], const uint32_t s[8], const uint32_t *ta, const uint32_t *tb,
+                          uint32_t inject) {
   uint32_t kr[9], sr[9];
-  recode_add<9, 8, kCombPos>(k.v, 8, kr);
-  recode_add<9, 8, kCombPos>(sig + 8, 8, sr);
-
+  recode_add<9, 8, kCombPos>(k, 8, kr);
+  recode_add<9, 8, kCombPos>(s, 8, sr);
   ge_ext q = ge_identity();
   HSV_NOUNROLL
   for (int j = 0; j < kCombPos; ++j) {
@@ -269,20 +224,36 @@ HSV_INL uint32_t verify_one_comb_k(uint32_t key_flags, const uint32_t sig[16], c
     q = ge_add_niels<true>(q, na);
     q = ge_add_niels<true>(q, select_niels<8>(tpb, cb));
   }
+  return q;
+}
 
-  fe rx, ry;
-  const uint32_t r_ok = ge_decompress(sig, rx, ry);
-  const uint32_t small_r = r_ok & y_is_small_order(ry);
-  const uint32_t same = ge_eq_affine(q, rx, ry);
-  const uint32_t a_ok = (key_flags & kKeyAOk) ? 1u : 0u;
-  const uint32_t small_a = a_ok & ((key_flags & kKeySmallA) ? 1u : 0u);
+// Verification against a cached committee key.  ta: the key's table of -A,
+// tb: the table of B, pk: the key's original 32 bytes (hashed as-is),
+// key_flags: kKeyAOk / kKeySmallA computed when the table was built.
+// Returns the same flag byte as verify_one for (pk, sig, msg), plus kFault
+// (fault_bit).  inject: fault injection (tests), applied to the first key entry.
+HSV_INL uint32_t verify_one_comb(const uint32_t pk[8], uint32_t key_flags, const uint32_t sig[16],
+                                 const uint32_t msg[8], const uint32_t *ta, const uint32_t *tb,
+                                 uint32_t inject = kInjectNone) {
+  const uint32_t s_ok = sc_is_canonical(sig + 8);
+  uint32_t h[16];
+  sha512_96(sig, pk, msg, h);
+  const sc k = sc_reduce512(h);
+  return comb_flags(s_ok, key_flags, sig, comb_walk8(k.v, sig + 8, ta, tb, inject));
+}
 
-  const uint32_t parse_ok = s_ok & a_ok & r_ok;
-  const uint32_t eq_ok = parse_ok & same;
-  const uint32_t strict_ok = eq_ok & (small_a ^ 1u) & (small_r ^ 1u);
-  return (strict_ok ? kStrictOk : 0u) | (eq_ok ? kEqOk : 0u) | (parse_ok ? kParseOk : 0u) |
-         (small_a ? kSmallA : 0u) | (small_r ? kSmallR : 0u) | (s_ok ? kSOk : 0u) |
-         (a_ok ? kAOk : 0u) | (r_ok ? kROk : 0u) | fault_bit(a_ok, r_ok, q);
+// The same after the hash: k = SHA-512(R || A || M) mod l, whatever the length
+// of M (the committee message path reads it from the route kernel's record,
+// hsv_committee_msgs.hip), so no key bytes are needed.  verify_one_comb's body
+// from the recoding on, kept as a function of its own: with verify_one_comb
+// written as the hash plus a call of this one, hipcc compiled
+// hsv_comb_verify_kernel and hsv_ctx_comb_kernel to two and three instructions
+// more than before; the two share the walk and the flag tail
+// instead.  tests/native/comb_k_host.cpp holds the two to the same byte.
+HSV_INL uint32_t verify_one_comb_k(uint32_t key_flags, const uint32_t sig[16], const sc &k, const uint32_t *ta,
+                                   const uint32_t *tb, uint32_t inject = kInjectNone) {
+  const uint32_t s_ok = sc_is_canonical(sig + 8);
+  return comb_flags(s_ok, key_flags, sig, comb_walk8(k.v, sig + 8, ta, tb, inject));
 }
 
 // ---- compact tables: 4-bit signed digits (HSV_COMMITTEE_DIGITS_COMPACT) --------
@@ -322,13 +293,10 @@ HSV_INL void comb4_build_group(const fe &x, const fe &y, uint32_t neg, int g, ui
       acc = ge_dbl<true>(acc);  // [16]base = 2 * [8]base
       bc = ge_to_cached(acc);
     }
-    uint32_t *e = out + i * kCombEntryWords;
-    fe_pack(acc.X, e);
-    fe_pack(acc.Y, e + 8);
-    fe_pack(acc.Z, e + 16);
-    pp = fe_mul(pp, acc.Z);
-    fe_pack(pp, tmp + i * 8);
+    comb_store_projective(acc, pp, out + i * kCombEntryWords, tmp + i * 8);
   }
+  // comb_normalise's loop, kept: through the shared one, counting up or down,
+  // hsv_comb4_build_kernel came out 13 - 14 instructions longer
   fe inv = fe_invert(pp);
   HSV_NOUNROLL
   for (int i = kComb4GroupEnt - 1; i >= 0; --i) {
@@ -386,19 +354,7 @@ HSV_INL uint32_t verify_one_comb4_k(uint32_t key_flags, const uint32_t sig[16], 
     q = ge_add_niels<true>(q, nb);
   }
 
-  fe rx, ry;
-  const uint32_t r_ok = ge_decompress(sig, rx, ry);
-  const uint32_t small_r = r_ok & y_is_small_order(ry);
-  const uint32_t same = ge_eq_affine(q, rx, ry);
-  const uint32_t a_ok = (key_flags & kKeyAOk) ? 1u : 0u;
-  const uint32_t small_a = a_ok & ((key_flags & kKeySmallA) ? 1u : 0u);
-
-  const uint32_t parse_ok = s_ok & a_ok & r_ok;
-  const uint32_t eq_ok = parse_ok & same;
-  const uint32_t strict_ok = eq_ok & (small_a ^ 1u) & (small_r ^ 1u);
-  return (strict_ok ? kStrictOk : 0u) | (eq_ok ? kEqOk : 0u) | (parse_ok ? kParseOk : 0u) |
-         (small_a ? kSmallA : 0u) | (small_r ? kSmallR : 0u) | (s_ok ? kSOk : 0u) |
-         (a_ok ? kAOk : 0u) | (r_ok ? kROk : 0u) | fault_bit(a_ok, r_ok, q);
+  return comb_flags(s_ok, key_flags, sig, q);
 }
 
 // verify_one_comb against a compact table: the hash of (R, pk, 32-byte
@@ -409,6 +365,23 @@ HSV_INL uint32_t verify_one_comb4(const uint32_t pk[8], uint32_t key_flags, cons
   uint32_t h[16];
   sha512_96(sig, pk, msg, h);
   return verify_one_comb4_k(key_flags, sig, sc_reduce512(h), ta, tb16, inject);
+}
+
+// The cores by table width, for bodies that are templates of it: DIGITS 8
+// (full tables, tb the 8-bit table of B) or 4 (compact, tb the wide comb of B).
+template <int DIGITS>
+HSV_INL uint32_t verify_comb(const uint32_t pk[8], uint32_t key_flags, const uint32_t sig[16], const uint32_t msg[8],
+                             const uint32_t *ta, const uint32_t *tb, uint32_t inject = kInjectNone) {
+  static_assert(DIGITS == 8 || DIGITS == 4, "table width");
+  if constexpr (DIGITS == 8) return verify_one_comb(pk, key_flags, sig, msg, ta, tb, inject);
+  else return verify_one_comb4(pk, key_flags, sig, msg, ta, tb, inject);
+}
+template <int DIGITS>
+HSV_INL uint32_t verify_comb_k(uint32_t key_flags, const uint32_t sig[16], const sc &k, const uint32_t *ta,
+                               const uint32_t *tb, uint32_t inject = kInjectNone) {
+  static_assert(DIGITS == 8 || DIGITS == 4, "table width");
+  if constexpr (DIGITS == 8) return verify_one_comb_k(key_flags, sig, k, ta, tb, inject);
+  else return verify_one_comb4_k(key_flags, sig, k, ta, tb, inject);
 }
 
 }  // namespace hsv

@@ -29,6 +29,19 @@
 
 namespace hsv {
 
+// The build kernels' prologue: key `key`'s encoding decompressed to (x, y);
+// the key's first lane group (group 0) writes its flag byte.
+__device__ __forceinline__ void comb_build_key(const uint8_t *__restrict__ encs, uint32_t key, uint32_t group,
+                                               uint8_t *__restrict__ key_flags, fe &x, fe &y) {
+  uint32_t w[8];
+  const uint4 *p = reinterpret_cast<const uint4 *>(encs + (uint64_t)key * 32);
+  const uint4 p0 = p[0], p1 = p[1];
+  w[0] = p0.x; w[1] = p0.y; w[2] = p0.z; w[3] = p0.w;
+  w[4] = p1.x; w[5] = p1.y; w[6] = p1.z; w[7] = p1.w;
+  const uint32_t ok = ge_decompress(w, x, y);
+  if (group == 0 && key_flags) key_flags[key] = (uint8_t)((ok ? kKeyAOk : 0u) | (ok && y_is_small_order(y) ? kKeySmallA : 0u));
+}
+
 __global__ void __launch_bounds__(256)
 hsv_comb_build_kernel(const uint8_t *__restrict__ encs, uint32_t nkeys, uint32_t npad, uint32_t negate,
                       uint32_t *__restrict__ tables, uint32_t *__restrict__ tmp,
@@ -36,17 +49,54 @@ hsv_comb_build_kernel(const uint8_t *__restrict__ encs, uint32_t nkeys, uint32_t
   const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t j = id / npad, key = id % npad;
   if (j >= (uint32_t)kCombPos || key >= nkeys) return;
-  uint32_t w[8];
-  const uint4 *p = reinterpret_cast<const uint4 *>(encs + (uint64_t)key * 32);
-  const uint4 p0 = p[0], p1 = p[1];
-  w[0] = p0.x; w[1] = p0.y; w[2] = p0.z; w[3] = p0.w;
-  w[4] = p1.x; w[5] = p1.y; w[6] = p1.z; w[7] = p1.w;
   fe x, y;
-  const uint32_t ok = ge_decompress(w, x, y);
-  if (j == 0 && key_flags) key_flags[key] = (uint8_t)((ok ? kKeyAOk : 0u) | (ok && y_is_small_order(y) ? kKeySmallA : 0u));
+  comb_build_key(encs, key, j, key_flags, x, y);
   const ge_ext base = comb_position_base(x, y, negate, (int)j);
   comb_build_position(base, tables + (uint64_t)key * kCombTableWords + (uint64_t)j * kCombEnt * kCombEntryWords,
                       tmp + (uint64_t)id * kCombEnt * 8);
+}
+
+// one vote's words: the key A, the signature (R, s) and the message digest M
+// (p / sp / gp: the vote's key encoding, signature and digest, in global
+// memory or LDS)
+__device__ __forceinline__ void load_vote_words(const uint4 *p, const uint4 *sp, const uint4 *gp, uint32_t pkw[8],
+                                                uint32_t sigw[16], uint32_t msgw[8]) {
+  const uint4 p0 = p[0], p1 = p[1];
+  const uint4 s0 = sp[0], s1 = sp[1], s2 = sp[2], s3 = sp[3];
+  const uint4 m0 = gp[0], m1 = gp[1];
+  pkw[0] = p0.x; pkw[1] = p0.y; pkw[2] = p0.z; pkw[3] = p0.w;
+  pkw[4] = p1.x; pkw[5] = p1.y; pkw[6] = p1.z; pkw[7] = p1.w;
+  sigw[0] = s0.x; sigw[1] = s0.y; sigw[2] = s0.z; sigw[3] = s0.w;
+  sigw[4] = s1.x; sigw[5] = s1.y; sigw[6] = s1.z; sigw[7] = s1.w;
+  sigw[8] = s2.x; sigw[9] = s2.y; sigw[10] = s2.z; sigw[11] = s2.w;
+  sigw[12] = s3.x; sigw[13] = s3.y; sigw[14] = s3.z; sigw[15] = s3.w;
+  msgw[0] = m0.x; msgw[1] = m0.y; msgw[2] = m0.z; msgw[3] = m0.w;
+  msgw[4] = m1.x; msgw[5] = m1.y; msgw[6] = m1.z; msgw[7] = m1.w;
+}
+
+// One verification per lane against a cached key, for either table width
+// (verify_comb<DIGITS>; tb: the table of B that width reads).  A vote whose key
+// index is out of range is verified against key 0 and gets flags 0.
+template <int DIGITS>
+__device__ __forceinline__ void comb_verify_lane(const uint32_t *__restrict__ key_idx, const uint8_t *__restrict__ sig,
+                                                 uint64_t sig_stride, const uint8_t *__restrict__ msg,
+                                                 uint64_t msg_stride, uint32_t m, const uint8_t *__restrict__ pks,
+                                                 const uint8_t *__restrict__ key_flags, uint32_t nkeys,
+                                                 const uint32_t *const *__restrict__ key_tables,
+                                                 const uint32_t *__restrict__ tb, uint8_t *__restrict__ flags_out,
+                                                 uint32_t inject, uint32_t *__restrict__ fault) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const uint32_t kidx = key_idx[i];
+  const bool kvalid = kidx < nkeys;
+  const uint32_t kk = kvalid ? kidx : 0u;
+  uint32_t pkw[8], sigw[16], msgw[8];
+  load_vote_words(reinterpret_cast<const uint4 *>(pks + (uint64_t)kk * 32),
+                  reinterpret_cast<const uint4 *>(sig + (uint64_t)i * sig_stride),
+                  reinterpret_cast<const uint4 *>(msg + (uint64_t)i * msg_stride), pkw, sigw, msgw);
+  const uint32_t f = verify_comb<DIGITS>(pkw, key_flags[kk], sigw, msgw, key_tables[kk], tb, inject);
+  if (f & kFault) fault[0] = 1u;  // device self-check (hsv_kernels.hip report_faults)
+  flags_out[i] = kvalid ? (uint8_t)f : (uint8_t)0;
 }
 
 __global__ void __launch_bounds__(256, 2)
@@ -56,31 +106,8 @@ hsv_comb_verify_kernel(const uint32_t *__restrict__ key_idx, const uint8_t *__re
                        uint32_t nkeys, const uint32_t *const *__restrict__ key_tables,
                        const uint32_t *__restrict__ btable, uint8_t *__restrict__ flags_out, uint32_t inject,
                        uint32_t *__restrict__ fault) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m) return;
-  const uint32_t kidx = key_idx[i];
-  const bool kvalid = kidx < nkeys;
-  const uint32_t kk = kvalid ? kidx : 0u;
-  uint32_t pkw[8], sigw[16], msgw[8];
-  {
-    const uint4 *p = reinterpret_cast<const uint4 *>(pks + (uint64_t)kk * 32);
-    const uint4 *s = reinterpret_cast<const uint4 *>(sig + (uint64_t)i * sig_stride);
-    const uint4 *g = reinterpret_cast<const uint4 *>(msg + (uint64_t)i * msg_stride);
-    const uint4 p0 = p[0], p1 = p[1];
-    const uint4 s0 = s[0], s1 = s[1], s2 = s[2], s3 = s[3];
-    const uint4 m0 = g[0], m1 = g[1];
-    pkw[0] = p0.x; pkw[1] = p0.y; pkw[2] = p0.z; pkw[3] = p0.w;
-    pkw[4] = p1.x; pkw[5] = p1.y; pkw[6] = p1.z; pkw[7] = p1.w;
-    sigw[0] = s0.x; sigw[1] = s0.y; sigw[2] = s0.z; sigw[3] = s0.w;
-    sigw[4] = s1.x; sigw[5] = s1.y; sigw[6] = s1.z; sigw[7] = s1.w;
-    sigw[8] = s2.x; sigw[9] = s2.y; sigw[10] = s2.z; sigw[11] = s2.w;
-    sigw[12] = s3.x; sigw[13] = s3.y; sigw[14] = s3.z; sigw[15] = s3.w;
-    msgw[0] = m0.x; msgw[1] = m0.y; msgw[2] = m0.z; msgw[3] = m0.w;
-    msgw[4] = m1.x; msgw[5] = m1.y; msgw[6] = m1.z; msgw[7] = m1.w;
-  }
-  const uint32_t f = verify_one_comb(pkw, key_flags[kk], sigw, msgw, key_tables[kk], btable, inject);
-  if (f & kFault) fault[0] = 1u;  // device self-check (hsv_kernels.hip report_faults)
-  flags_out[i] = kvalid ? (uint8_t)f : (uint8_t)0;
+  comb_verify_lane<8>(key_idx, sig, sig_stride, msg, msg_stride, m, pks, key_flags, nkeys, key_tables, btable,
+                      flags_out, inject, fault);
 }
 
 // Latency form of hsv_comb_verify_kernel for small batches (a QC is 67 or
@@ -195,24 +222,6 @@ __device__ uint64_t g_qc_clk[kQcClkWaves][kQcClkSlots];
 // C3 kernel 4.4-4.6 us behind C1 either way, and the barrier ahead of every
 // wave cost C1 3.5 us (profiles/r04i_qc_ab_stage.txt).  The resident service
 // does stage its request in LDS, read in one load by wave 0 (below).
-
-// one vote's words: the key A, the signature (R, s) and the message digest M
-// (p / sp / gp: the vote's key encoding, signature and digest, in global
-// memory or LDS)
-__device__ __forceinline__ void load_vote_words(const uint4 *p, const uint4 *sp, const uint4 *gp, uint32_t pkw[8],
-                                                uint32_t sigw[16], uint32_t msgw[8]) {
-  const uint4 p0 = p[0], p1 = p[1];
-  const uint4 s0 = sp[0], s1 = sp[1], s2 = sp[2], s3 = sp[3];
-  const uint4 m0 = gp[0], m1 = gp[1];
-  pkw[0] = p0.x; pkw[1] = p0.y; pkw[2] = p0.z; pkw[3] = p0.w;
-  pkw[4] = p1.x; pkw[5] = p1.y; pkw[6] = p1.z; pkw[7] = p1.w;
-  sigw[0] = s0.x; sigw[1] = s0.y; sigw[2] = s0.z; sigw[3] = s0.w;
-  sigw[4] = s1.x; sigw[5] = s1.y; sigw[6] = s1.z; sigw[7] = s1.w;
-  sigw[8] = s2.x; sigw[9] = s2.y; sigw[10] = s2.z; sigw[11] = s2.w;
-  sigw[12] = s3.x; sigw[13] = s3.y; sigw[14] = s3.z; sigw[15] = s3.w;
-  msgw[0] = m0.x; msgw[1] = m0.y; msgw[2] = m0.z; msgw[3] = m0.w;
-  msgw[4] = m1.x; msgw[5] = m1.y; msgw[6] = m1.z; msgw[7] = m1.w;
-}
 
 // lane g's 8 P digit bits of a recoded scalar, starting at bit 8 g P
 __device__ __forceinline__ uint64_t lane_digits(const uint32_t r[9], uint32_t g) {
@@ -597,14 +606,8 @@ hsv_comb4_build_kernel(const uint8_t *__restrict__ encs, uint32_t nkeys, uint32_
   const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t g = id / npad, key = id % npad;
   if (g >= (uint32_t)kComb4Groups || key >= nkeys) return;
-  uint32_t w[8];
-  const uint4 *p = reinterpret_cast<const uint4 *>(encs + (uint64_t)key * 32);
-  const uint4 p0 = p[0], p1 = p[1];
-  w[0] = p0.x; w[1] = p0.y; w[2] = p0.z; w[3] = p0.w;
-  w[4] = p1.x; w[5] = p1.y; w[6] = p1.z; w[7] = p1.w;
   fe x, y;
-  const uint32_t ok = ge_decompress(w, x, y);
-  if (g == 0 && key_flags) key_flags[key] = (uint8_t)((ok ? kKeyAOk : 0u) | (ok && y_is_small_order(y) ? kKeySmallA : 0u));
+  comb_build_key(encs, key, g, key_flags, x, y);
   comb4_build_group(x, y, negate, (int)g, tables + (uint64_t)key * kComb4TableWords,
                     tmp + (uint64_t)id * kComb4GroupEnt * 8);
 }
@@ -619,18 +622,8 @@ hsv_comb4_verify_kernel(const uint32_t *__restrict__ key_idx, const uint8_t *__r
                         uint32_t nkeys, const uint32_t *const *__restrict__ key_tables,
                         const uint32_t *__restrict__ comb16, uint8_t *__restrict__ flags_out, uint32_t inject,
                         uint32_t *__restrict__ fault) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m) return;
-  const uint32_t kidx = key_idx[i];
-  const bool kvalid = kidx < nkeys;
-  const uint32_t kk = kvalid ? kidx : 0u;
-  uint32_t pkw[8], sigw[16], msgw[8];
-  load_vote_words(reinterpret_cast<const uint4 *>(pks + (uint64_t)kk * 32),
-                  reinterpret_cast<const uint4 *>(sig + (uint64_t)i * sig_stride),
-                  reinterpret_cast<const uint4 *>(msg + (uint64_t)i * msg_stride), pkw, sigw, msgw);
-  const uint32_t f = verify_one_comb4(pkw, key_flags[kk], sigw, msgw, key_tables[kk], comb16, inject);
-  if (f & kFault) fault[0] = 1u;  // device self-check (hsv_kernels.hip report_faults)
-  flags_out[i] = kvalid ? (uint8_t)f : (uint8_t)0;
+  comb_verify_lane<4>(key_idx, sig, sig_stride, msg, msg_stride, m, pks, key_flags, nkeys, key_tables, comb16,
+                      flags_out, inject, fault);
 }
 
 // one lane per (position j, chunk c) of the wide B table; j is wave-uniform

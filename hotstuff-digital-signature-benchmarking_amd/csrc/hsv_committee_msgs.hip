@@ -33,39 +33,20 @@
 #include "hsv_msgwave.hpp"
 #include "hsv_verify_hc.hpp"
 #include "hsv_pointpass.hpp"
+#include "hsv_routed.hpp"
 
 namespace hsv {
 
-struct CmsgCounters {  // zeroed before the route launch (32 bytes)
-  uint32_t hits, misses, fb_count;  // list lengths, written by the route kernel
-  uint32_t hit_next, gen_next;      // work counters of the comb and the generic pass
-  uint32_t pad[3];
-};
-
-// this lane's place among the set bits of a wave mask
-__device__ __forceinline__ uint32_t cmsg_rank(uint64_t mask, uint32_t lane) {
-  return (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-}
-
-__device__ __forceinline__ void load_words8(const uint8_t *p, uint32_t w[8]) {
-  const uint4 *q = reinterpret_cast<const uint4 *>(p);
-  const uint4 a = q[0], b = q[1];
-  w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
-  w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-}
-
-// One lane per item.  The lists are compacted per wave as hsv_ctx_route_kernel
-// does: one ballot, one atomic add by one lane per list, a prefix rank.  Every
-// store and atomic sits after the hash loop (msg_hash_lane), where no loop
-// surrounds them, so they may sit in lane-dependent regions; a lane past n
-// redoes item n - 1 in the loop and stores nothing.
+// One lane per item; the list compaction's rules: hsv_routed.hpp.  Every store
+// and atomic sits after the hash loop (msg_hash_lane), so no loop surrounds
+// them; a lane past n redoes item n - 1 in that loop and stores nothing.
 // krec: k mod l of the members' items, eight words, row stride n.
 __global__ void __launch_bounds__(kMsgBlock)
 hsv_cmsg_route_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const uint8_t *__restrict__ sig,
                       uint64_t sig_stride, const uint8_t *__restrict__ msgs, const uint64_t *__restrict__ offsets,
                       uint64_t msg_len, uint64_t msg_stride, uint32_t n, const uint32_t *__restrict__ keytab,
                       uint32_t keymask, uint64_t seed, const uint8_t *__restrict__ pks, uint32_t nkeys,
-                      CmsgCounters *__restrict__ ctr, uint2 *__restrict__ hit_list, uint32_t *__restrict__ miss_list,
+                      RoutedCounters *__restrict__ ctr, uint2 *__restrict__ hit_list, uint32_t *__restrict__ miss_list,
                       uint32_t *__restrict__ krec, uint32_t *__restrict__ prep, uint32_t *__restrict__ fb_list,
                       int lat_bits, uint8_t *__restrict__ flags_out) {
   __shared__ uint4 stage_all[kMsgWaves][64 * kMsgQ];
@@ -92,14 +73,14 @@ hsv_cmsg_route_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const 
   if (lane < 2u && cnt) base = atomicAdd(lane ? &ctr->misses : &ctr->hits, cnt);
   const uint32_t hb = (uint32_t)__shfl((int)base, 0), mb = (uint32_t)__shfl((int)base, 1);
   if (hit) {  // the comb route takes k mod l as it is: no lattice reduction
-    hit_list[hb + cmsg_rank(hm, lane)] = make_uint2(i, kidx);
+    hit_list[hb + mask_rank(hm, lane)] = make_uint2(i, kidx);
     const sc k = sc_reduce512(hw);
     HSV_UNROLL
     for (int j = 0; j < 8; ++j) krec[(uint64_t)j * n + i] = k.v[j];
   }
   bool fb = false;
   if (miss) {
-    miss_list[mb + cmsg_rank(mm, lane)] = i;
+    miss_list[mb + mask_rank(mm, lane)] = i;
     uint32_t s[8];
     load_words8(sigi + 32, s);
     fb = prep_from_hash<4, PutPlain, true>(hw, s, prep + i, n, lat_bits);
@@ -109,82 +90,67 @@ hsv_cmsg_route_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const 
     uint32_t fbase = 0;
     if (lane == 0u) fbase = atomicAdd(&ctr->fb_count, (uint32_t)__popcll(fm));
     fbase = (uint32_t)__shfl((int)fbase, 0);
-    if (fb) fb_list[fbase + cmsg_rank(fm, lane)] = i;
+    if (fb) fb_list[fbase + mask_rank(fm, lane)] = i;
   }
 }
 
-// The comb pass over the hit list (patterned on hsv_ctx_comb_kernel): R || s in
-// place from the caller's sig array, k from the k record, the member's tables
-// by its index.  A lane past the list's end redoes the batch's first entry and
-// stores the same byte and bit again, so no store of the work loop depends on
-// the lane's place in the list.
+// The comb pass over the hit list (patterned on hsv_ctx_comb_kernel), for
+// either table width (DIGITS 8: tb the 8-bit table of B; 4: the wide comb of
+// B): R || s in place from the caller's sig array, k from the k record, the
+// member's tables by its index.  The work loop's rules: hsv_routed.hpp.
+template <int DIGITS>
+__device__ __forceinline__ void cmsg_comb_pass(const uint8_t *sig, uint64_t sig_stride, uint32_t n, RoutedCounters *ctr,
+                                               const uint2 *hit_list, const uint32_t *krec, const uint8_t *key_flags,
+                                               uint32_t nkeys, const uint32_t *const *key_tables, const uint32_t *tb,
+                                               uint8_t *flags_out, uint32_t *strict_bits, uint32_t inject,
+                                               uint32_t *fault) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t nh = min((uint32_t)__builtin_amdgcn_readfirstlane(ctr->hits), n);
+  uint32_t bad = 0;
+  for (;;) {
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(&ctr->hit_next, 64u);
+    base = __builtin_amdgcn_readfirstlane(__shfl(base, 0));
+    if (base >= nh) break;
+    const uint32_t j = base + lane;
+    const uint2 e = hit_list[j < nh ? j : base];
+    const uint32_t i = min(e.x, n - 1u), kk = e.y < nkeys ? e.y : 0u;  // (the route kernel wrote both in range)
+    uint32_t sigw[16];
+    load_words8(sig + (uint64_t)i * sig_stride, sigw);
+    load_words8(sig + (uint64_t)i * sig_stride + 32, sigw + 8);
+    sc k;
+    HSV_UNROLL
+    for (int w = 0; w < 8; ++w) k.v[w] = krec[(uint64_t)w * n + i];
+    const uint32_t f = verify_comb_k<DIGITS>(key_flags[kk], sigw, k, key_tables[kk], tb, inject);
+    bad |= (f & kFault) ? 1u : 0u;
+    store_verdict(flags_out, strict_bits, i, f);
+  }
+  report_faults(fault, bad);
+}
+
 __global__ void __launch_bounds__(256, 2)
-hsv_cmsg_comb_kernel(const uint8_t *__restrict__ sig, uint64_t sig_stride, uint32_t n, CmsgCounters *__restrict__ ctr,
+hsv_cmsg_comb_kernel(const uint8_t *__restrict__ sig, uint64_t sig_stride, uint32_t n, RoutedCounters *__restrict__ ctr,
                      const uint2 *__restrict__ hit_list, const uint32_t *__restrict__ krec,
                      const uint8_t *__restrict__ key_flags, uint32_t nkeys,
                      const uint32_t *const *__restrict__ key_tables, const uint32_t *__restrict__ btable,
                      uint8_t *__restrict__ flags_out, uint32_t *__restrict__ strict_bits, uint32_t inject,
                      uint32_t *__restrict__ fault) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t nh = min((uint32_t)__builtin_amdgcn_readfirstlane(ctr->hits), n);
-  uint32_t bad = 0;
-  for (;;) {
-    uint32_t base = 0;
-    if (lane == 0) base = atomicAdd(&ctr->hit_next, 64u);
-    base = __builtin_amdgcn_readfirstlane(__shfl(base, 0));
-    if (base >= nh) break;
-    const uint32_t j = base + lane;
-    const uint2 e = hit_list[j < nh ? j : base];
-    const uint32_t i = min(e.x, n - 1u), kk = e.y < nkeys ? e.y : 0u;  // (the route kernel wrote both in range)
-    uint32_t sigw[16];
-    load_words8(sig + (uint64_t)i * sig_stride, sigw);
-    load_words8(sig + (uint64_t)i * sig_stride + 32, sigw + 8);
-    sc k;
-    HSV_UNROLL
-    for (int w = 0; w < 8; ++w) k.v[w] = krec[(uint64_t)w * n + i];
-    const uint32_t f = verify_one_comb_k(key_flags[kk], sigw, k, key_tables[kk], btable, inject);
-    bad |= (f & kFault) ? 1u : 0u;
-    if (flags_out) flags_out[i] = (uint8_t)f;
-    if (strict_bits && (f & kStrictOk)) atomicOr(&strict_bits[i >> 5], 1u << (i & 31u));
-  }
-  report_faults(fault, bad);
+  cmsg_comb_pass<8>(sig, sig_stride, n, ctr, hit_list, krec, key_flags, nkeys, key_tables, btable, flags_out,
+                    strict_bits, inject, fault);
 }
 
 // hsv_cmsg_comb_kernel for a committee with compact (4-bit digit) tables
 // (verify_one_comb4_k: 80 mixed additions and one decompression; comb16: the
-// wide comb of B, where hsv_cmsg_comb_kernel reads the narrow one): the same
-// dealing from hit_next, the same redone first entry past the list's end, the
-// same stores.
+// wide comb of B, where hsv_cmsg_comb_kernel reads the narrow one).
 __global__ void __launch_bounds__(256, 2)
-hsv_cmsg_comb4_kernel(const uint8_t *__restrict__ sig, uint64_t sig_stride, uint32_t n, CmsgCounters *__restrict__ ctr,
+hsv_cmsg_comb4_kernel(const uint8_t *__restrict__ sig, uint64_t sig_stride, uint32_t n, RoutedCounters *__restrict__ ctr,
                       const uint2 *__restrict__ hit_list, const uint32_t *__restrict__ krec,
                       const uint8_t *__restrict__ key_flags, uint32_t nkeys,
                       const uint32_t *const *__restrict__ key_tables, const uint32_t *__restrict__ comb16,
                       uint8_t *__restrict__ flags_out, uint32_t *__restrict__ strict_bits, uint32_t inject,
                       uint32_t *__restrict__ fault) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t nh = min((uint32_t)__builtin_amdgcn_readfirstlane(ctr->hits), n);
-  uint32_t bad = 0;
-  for (;;) {
-    uint32_t base = 0;
-    if (lane == 0) base = atomicAdd(&ctr->hit_next, 64u);
-    base = __builtin_amdgcn_readfirstlane(__shfl(base, 0));
-    if (base >= nh) break;
-    const uint32_t j = base + lane;
-    const uint2 e = hit_list[j < nh ? j : base];
-    const uint32_t i = min(e.x, n - 1u), kk = e.y < nkeys ? e.y : 0u;  // (the route kernel wrote both in range)
-    uint32_t sigw[16];
-    load_words8(sig + (uint64_t)i * sig_stride, sigw);
-    load_words8(sig + (uint64_t)i * sig_stride + 32, sigw + 8);
-    sc k;
-    HSV_UNROLL
-    for (int w = 0; w < 8; ++w) k.v[w] = krec[(uint64_t)w * n + i];
-    const uint32_t f = verify_one_comb4_k(key_flags[kk], sigw, k, key_tables[kk], comb16, inject);
-    bad |= (f & kFault) ? 1u : 0u;
-    if (flags_out) flags_out[i] = (uint8_t)f;
-    if (strict_bits && (f & kStrictOk)) atomicOr(&strict_bits[i >> 5], 1u << (i & 31u));
-  }
-  report_faults(fault, bad);
+  cmsg_comb_pass<4>(sig, sig_stride, n, ctr, hit_list, krec, key_flags, nkeys, key_tables, comb16, flags_out,
+                    strict_bits, inject, fault);
 }
 
 // hsv_ctx_generic_kernel (hsv_mempool.hip) with pk, R and s read in place from
@@ -200,7 +166,7 @@ hsv_cmsg_generic_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, cons
                         uint64_t sig_stride, uint32_t n, uint8_t *__restrict__ flags_out,
                         uint32_t *__restrict__ strict_bits, uint4 *__restrict__ vt_ws,
                         const uint32_t *__restrict__ comb_b, const uint32_t *__restrict__ rec,
-                        CmsgCounters *__restrict__ ctr, const uint32_t *__restrict__ miss_list,
+                        RoutedCounters *__restrict__ ctr, const uint32_t *__restrict__ miss_list,
                         const uint32_t *__restrict__ fb_list, uint32_t *__restrict__ canary, uint32_t nonce,
                         uint32_t inject, uint32_t *__restrict__ fault, uint64_t *__restrict__ totals) {
   constexpr int kEnt = (1 << (WA - 1)) + 1;
@@ -237,10 +203,7 @@ hsv_cmsg_generic_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, cons
       for (int w = 0; w < 8; ++w) k.v[w] = rec[(10ull + (uint64_t)w) * n + idx];
       const uint32_t f = verify_one_full_comb<WA, false, CB>(pkw, sigw, k, comb_b, vt);
       bad |= ((f & kFault) ? 1u : 0u) | (canary[slot] != nonce ? 2u : 0u);
-      if (valid) {
-        if (flags_out) flags_out[idx] = (uint8_t)f;
-        if (strict_bits && (f & kStrictOk)) atomicOr(&strict_bits[idx >> 5], 1u << (idx & 31u));
-      }
+      if (valid) store_verdict(flags_out, strict_bits, idx, f);
       continue;
     }
     const uint32_t b0 = base - fb_end;
@@ -253,10 +216,7 @@ hsv_cmsg_generic_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, cons
     const bool own = valid && !(meta & kPrepFallback);
     const uint32_t f = verify_one_prepped<WA, CB>(pkw, rw, rec + li, n, meta, comb_b, vt);
     bad |= ((f & kFault) ? 1u : 0u) | (canary[slot] != nonce ? 2u : 0u);
-    if (own) {
-      if (flags_out) flags_out[li] = (uint8_t)f;
-      if (strict_bits && (f & kStrictOk)) atomicOr(&strict_bits[li >> 5], 1u << (li & 31u));
-    }
+    if (own) store_verdict(flags_out, strict_bits, li, f);
   }
   report_faults(fault, bad);
 }
@@ -264,45 +224,11 @@ hsv_cmsg_generic_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, cons
 }  // namespace hsv
 
 // ---- one round of hsv_committee_verify_msgs* -----------------------------------
-namespace {
-// blocks per CU of the two persistent passes and the device's CUs, cached per device
-struct CmsgGrids {
-  int comb_bpc, generic_bpc, cus;
-  int comb4_bpc;  // the compact comb pass, from its own occupancy query
-};
-hipError_t cmsg_grids(int dev, CmsgGrids *out) {
-  static std::mutex mu;
-  static std::unordered_map<int, CmsgGrids> per_dev;
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = per_dev.find(dev);
-  if (it == per_dev.end()) {
-    int bc = 0, bc4 = 0, bg = 0, cus = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &bc, reinterpret_cast<const void *>(hsv::hsv_cmsg_comb_kernel), 256, 0);
-    if (e == hipSuccess)
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-          &bc4, reinterpret_cast<const void *>(hsv::hsv_cmsg_comb4_kernel), 256, 0);
-    if (e == hipSuccess)
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-          &bg, reinterpret_cast<const void *>(hsv::hsv_cmsg_generic_kernel<4, HSV_HP_WAVES, 16>), hsv::kBlock, 0);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return e;
-    it = per_dev.emplace(dev, CmsgGrids{std::max(1, bc), std::max(1, bg), std::max(1, cus), std::max(1, bc4)}).first;
-  }
-  *out = it->second;
-  return hipSuccess;
-}
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-}  // namespace
-
-// n <= 2^22 items (current device, no synchronisation): counters and strict
-// words zeroed on the stream, then the route kernel, the comb pass and the
-// generic pass.  Both persistent grids are sized as hsv_launch_committee_tx's:
-// occupancy x CUs, one CU left free once the resident service has run, capped
-// by ceil(n / 256) -- the host knows n, not the split.  Workspace from the
-// library pool: per-lane tables | counters | canaries | k record | hit list |
-// miss list | fallback list | prepass words.  No 128-byte records: the passes
-// read pk and sig in place.
+// n <= 2^22 items: the round of hsv_routed.hpp (RoutedRound: grids, memsets,
+// the comb pass by table width).  Workspace from the library pool: per-lane
+// tables | counters | canaries | k record | hit list | miss list | fallback
+// list | prepass words.  No 128-byte records: the passes read pk and sig in
+// place.
 extern "C" hipError_t hsv_launch_committee_msgs(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig,
                                                 uint64_t sig_stride, const uint8_t *msgs, const uint64_t *offsets,
                                                 uint64_t msg_len, uint64_t msg_stride, uint32_t n,
@@ -316,37 +242,27 @@ extern "C" hipError_t hsv_launch_committee_msgs(const uint8_t *pk, uint64_t pk_s
   if (n > (1u << 22) || (digit_bits != 8 && digit_bits != 4) || !pk || !sig || !btable || !comb16 || !fault ||
       (nkeys && (!keytab || !pks || !key_flags || !key_tables)))
     return hipErrorInvalidValue;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  hsv::RoutedRound r;
+  hipError_t e = r.size(n, digit_bits, reinterpret_cast<const void *>(hsv::hsv_cmsg_comb_kernel),
+                        reinterpret_cast<const void *>(hsv::hsv_cmsg_comb4_kernel),
+                        reinterpret_cast<const void *>(hsv::hsv_cmsg_generic_kernel<4, HSV_HP_WAVES, 16>));
   if (e != hipSuccess) return e;
-  CmsgGrids g;
-  e = cmsg_grids(dev, &g);
-  if (e != hipSuccess) return e;
-  const int cus = hsvi_resident_started() && g.cus > 1 ? g.cus - 1 : g.cus;
-  const uint32_t blocks_needed = (n + hsv::kBlock - 1) / hsv::kBlock;
-  const uint32_t grid_c =
-      std::min<uint32_t>(blocks_needed, (uint32_t)((digit_bits == 4 ? g.comb4_bpc : g.comb_bpc) * cus));
-  const uint32_t grid_g = std::min<uint32_t>(blocks_needed, (uint32_t)(g.generic_bpc * cus));
-  const size_t vt_bytes = (size_t)grid_g * hsv::kBlock * hsv::vt_lane_uint4<4>() * sizeof(uint4);
-  const size_t canary_bytes = up256((size_t)grid_g * hsv::kBlock * sizeof(uint32_t));
-  const size_t krec_bytes = up256((size_t)n * 32), hit_bytes = up256((size_t)n * sizeof(uint2));
-  const size_t list_bytes = up256((size_t)n * sizeof(uint32_t));
+  const size_t krec_bytes = hsv::up256((size_t)n * 32), hit_bytes = hsv::up256((size_t)n * sizeof(uint2));
+  const size_t list_bytes = hsv::up256((size_t)n * sizeof(uint32_t));
   const size_t prep_bytes = (size_t)n * hsv::kPrepWords * sizeof(uint32_t);
-  const size_t need = vt_bytes + 256 + canary_bytes + krec_bytes + hit_bytes + 2 * list_bytes + prep_bytes;
-  hsv::Workspace ws(nullptr, 0, need, stream);
+  hsv::Workspace ws(nullptr, 0, r.head_bytes() + krec_bytes + hit_bytes + 2 * list_bytes + prep_bytes, stream);
   if (ws.status() != hipSuccess) return ws.status();
   uint8_t *p = ws.get();
   uint4 *vt_ws = reinterpret_cast<uint4 *>(p);
-  hsv::CmsgCounters *ctr = reinterpret_cast<hsv::CmsgCounters *>(p += vt_bytes);
+  hsv::RoutedCounters *ctr = reinterpret_cast<hsv::RoutedCounters *>(p += r.vt_bytes);
   uint32_t *canary = reinterpret_cast<uint32_t *>(p += 256);
-  uint32_t *krec = reinterpret_cast<uint32_t *>(p += canary_bytes);
+  uint32_t *krec = reinterpret_cast<uint32_t *>(p += r.canary_bytes);
   uint2 *hit_list = reinterpret_cast<uint2 *>(p += krec_bytes);
   uint32_t *miss_list = reinterpret_cast<uint32_t *>(p += hit_bytes);
   uint32_t *fb_list = reinterpret_cast<uint32_t *>(p += list_bytes);
   uint32_t *prep = reinterpret_cast<uint32_t *>(p += list_bytes);
   const uint32_t inject = (uint32_t)hsvi_inject_mode();
-  e = hipMemsetAsync(ctr, 0, sizeof(hsv::CmsgCounters), stream);
-  if (e == hipSuccess && strict_bits) e = hipMemsetAsync(strict_bits, 0, (size_t)((n + 31u) / 32u) * 4u, stream);
+  e = hsv::RoutedRound::zero(ctr, strict_bits, n, stream);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(hsv::hsv_cmsg_route_kernel, dim3((n + hsv::kMsgBlock - 1) / hsv::kMsgBlock),
                        dim3(hsv::kMsgBlock), 0, stream, pk, pk_stride, sig, sig_stride, msgs, offsets, msg_len,
@@ -354,17 +270,14 @@ extern "C" hipError_t hsv_launch_committee_msgs(const uint8_t *pk, uint64_t pk_s
                        hsvi_lattice_bits(), flags_out);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) {  // the committee's table width decides the comb pass, nothing else
-    if (digit_bits == 4)
-      hipLaunchKernelGGL(hsv::hsv_cmsg_comb4_kernel, dim3(grid_c), dim3(256), 0, stream, sig, sig_stride, n, ctr,
-                         hit_list, krec, key_flags, nkeys, key_tables, comb16, flags_out, strict_bits, inject, fault);
-    else
-      hipLaunchKernelGGL(hsv::hsv_cmsg_comb_kernel, dim3(grid_c), dim3(256), 0, stream, sig, sig_stride, n, ctr, hit_list,
-                         krec, key_flags, nkeys, key_tables, btable, flags_out, strict_bits, inject, fault);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(r.pick(hsv::hsv_cmsg_comb_kernel, hsv::hsv_cmsg_comb4_kernel), dim3(r.grid_c), dim3(256), 0,
+                       stream, sig, sig_stride, n, ctr, hit_list, krec, key_flags, nkeys, key_tables,
+                       r.pick(btable, comb16), flags_out, strict_bits, inject, fault);
     e = hipGetLastError();
   }
   if (e == hipSuccess) {
-    hipLaunchKernelGGL((hsv::hsv_cmsg_generic_kernel<4, HSV_HP_WAVES, 16>), dim3(grid_g), dim3(hsv::kBlock), 0, stream,
+    hipLaunchKernelGGL((hsv::hsv_cmsg_generic_kernel<4, HSV_HP_WAVES, 16>), dim3(r.grid_g), dim3(hsv::kBlock), 0, stream,
                        pk, pk_stride, sig, sig_stride, n, flags_out, strict_bits, vt_ws, comb16, prep, ctr, miss_list,
                        fb_list, canary, hsvi_next_nonce(), inject, fault, totals);
     e = hipGetLastError();

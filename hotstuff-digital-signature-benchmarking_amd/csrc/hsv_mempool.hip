@@ -36,6 +36,7 @@
 #include "hsv_txhash.hpp"
 #include "hsv_verify_hc.hpp"
 #include "hsv_pointpass.hpp"
+#include "hsv_routed.hpp"
 
 namespace hsv {
 
@@ -328,7 +329,7 @@ hsv_verify_tx_fused_kernel(const uint8_t *__restrict__ txs, const uint64_t *__re
       load_triple(records, 128, records + 32, 128, records + 96, 128, idx, pkw, sigw, msgw);
       const uint32_t f = verify_one_full_comb<WA, false, CB>(pkw, sigw, msgw, comb_b, vt);
       bad |= ((f & kFault) ? 1u : 0u) | (canary[slot] != nonce ? 2u : 0u);
-      if (valid) {
+      if (valid) {  // store_verdict written out: through the call this kernel came out 3 instructions longer
         if (flags_out) flags_out[idx] = (uint8_t)f;
         if (strict_bits && (f & kStrictOk)) atomicOr(&strict_bits[idx >> 5], 1u << (idx & 31u));
       }
@@ -370,25 +371,12 @@ __global__ void __launch_bounds__(kTxBlock) hsv_tx_mask_kernel(const uint64_t *_
 // Flags are those of hsv_verify_transactions* bit for bit: verify_one_comb and
 // the point pass return the same byte for the same (pk, sig, digest), and a
 // hit means the 32 pk bytes equal the member's.
-struct CtxCounters {  // zeroed before the route launch (32 bytes)
-  uint32_t hits, misses, fb_count;  // list lengths, written by the route kernel
-  uint32_t hit_next, gen_next;      // work counters of the comb and the generic pass
-  uint32_t pad[3];
-};
-
-// this lane's place among the set bits of a wave mask
-__device__ __forceinline__ uint32_t mask_rank(uint64_t mask, uint32_t lane) {
-  return (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-}
-
-// The lists are compacted per wave: one ballot, one atomic add by one lane,
-// a prefix count -- entries keep their order inside a wave, and a list costs
-// one atomic per wave.  No loop surrounds the stores (one lane per
-// transaction), so they may sit in lane-dependent regions.
+// The passes' and the list compaction's rules: hsv_routed.hpp.
+// One lane per transaction, so no loop surrounds the list stores.
 __global__ void __launch_bounds__(kTxBlock)
 hsv_ctx_route_kernel(const uint8_t *__restrict__ txs, const uint64_t *__restrict__ offsets, uint64_t tx_size, uint32_t n,
                      uint4 *__restrict__ rec, const uint32_t *__restrict__ keytab, uint32_t keymask, uint64_t seed,
-                     const uint8_t *__restrict__ pks, uint32_t nkeys, CtxCounters *__restrict__ ctr,
+                     const uint8_t *__restrict__ pks, uint32_t nkeys, RoutedCounters *__restrict__ ctr,
                      uint2 *__restrict__ hit_list, uint32_t *__restrict__ miss_list, uint32_t *__restrict__ prep,
                      uint32_t *__restrict__ fb_list, int lat_bits, uint8_t *__restrict__ flags_out) {
   __shared__ uint4 stage_all[kTxWaves][64 * kTxQ];
@@ -429,11 +417,9 @@ hsv_ctx_route_kernel(const uint8_t *__restrict__ txs, const uint64_t *__restrict
   }
 }
 
-// A lane past the list's end redoes the batch's first entry and stores the
-// same byte and bit again, so no store of the work loop depends on the lane's
-// place in the list.
+// The comb pass over the hit list (its work loop's rules: hsv_routed.hpp).
 __global__ void __launch_bounds__(256, 2)
-hsv_ctx_comb_kernel(const uint8_t *__restrict__ records, uint32_t n, CtxCounters *__restrict__ ctr,
+hsv_ctx_comb_kernel(const uint8_t *__restrict__ records, uint32_t n, RoutedCounters *__restrict__ ctr,
                     const uint2 *__restrict__ hit_list, const uint8_t *__restrict__ pks,
                     const uint8_t *__restrict__ key_flags, uint32_t nkeys,
                     const uint32_t *const *__restrict__ key_tables, const uint32_t *__restrict__ btable,
@@ -457,19 +443,18 @@ hsv_ctx_comb_kernel(const uint8_t *__restrict__ records, uint32_t n, CtxCounters
     }
     const uint32_t f = verify_one_comb(pkw, key_flags[kk], sigw, msgw, key_tables[kk], btable, inject);
     bad |= (f & kFault) ? 1u : 0u;
-    if (flags_out) flags_out[i] = (uint8_t)f;
-    if (strict_bits && (f & kStrictOk)) atomicOr(&strict_bits[i >> 5], 1u << (i & 31u));
+    store_verdict(flags_out, strict_bits, i, f);
   }
   report_faults(fault, bad);
 }
 
 // hsv_ctx_comb_kernel for a committee with compact (4-bit digit) tables
 // (verify_one_comb4: 80 mixed additions and one decompression; comb16: the
-// wide comb of B, where hsv_ctx_comb_kernel reads the narrow one): the same
-// dealing from hit_next, the same redone first entry past the list's end, the
-// same stores.
+// wide comb of B, where hsv_ctx_comb_kernel reads the narrow one).  A twin,
+// not a template of the width: as one body both compiled 10 instructions
+// longer.
 __global__ void __launch_bounds__(256, 2)
-hsv_ctx_comb4_kernel(const uint8_t *__restrict__ records, uint32_t n, CtxCounters *__restrict__ ctr,
+hsv_ctx_comb4_kernel(const uint8_t *__restrict__ records, uint32_t n, RoutedCounters *__restrict__ ctr,
                      const uint2 *__restrict__ hit_list, const uint8_t *__restrict__ pks,
                      const uint8_t *__restrict__ key_flags, uint32_t nkeys,
                      const uint32_t *const *__restrict__ key_tables, const uint32_t *__restrict__ comb16,
@@ -493,8 +478,7 @@ hsv_ctx_comb4_kernel(const uint8_t *__restrict__ records, uint32_t n, CtxCounter
     }
     const uint32_t f = verify_one_comb4(pkw, key_flags[kk], sigw, msgw, key_tables[kk], comb16, inject);
     bad |= (f & kFault) ? 1u : 0u;
-    if (flags_out) flags_out[i] = (uint8_t)f;
-    if (strict_bits && (f & kStrictOk)) atomicOr(&strict_bits[i >> 5], 1u << (i & 31u));
+    store_verdict(flags_out, strict_bits, i, f);
   }
   report_faults(fault, bad);
 }
@@ -505,12 +489,14 @@ hsv_ctx_comb4_kernel(const uint8_t *__restrict__ records, uint32_t n, CtxCounter
 // records at stride 128, the prepass words at rec + i, row stride n.
 // totals (diagnostics, hsv_test_committee_tx_counts): one lane adds the
 // round's list lengths {hits, misses, fallback items}.
+// (hsv_cmsg_generic_kernel is the same loop with other loads; its rules are
+// hsv_routed.hpp's, and DESIGN.md 4j says why the two stay apart.)
 template <int WA, int WAVES, int CB>
 __global__ void __launch_bounds__(kBlock, WAVES)
 hsv_ctx_generic_kernel(const uint8_t *__restrict__ records, uint32_t n, uint8_t *__restrict__ flags_out,
                        uint32_t *__restrict__ strict_bits, uint4 *__restrict__ vt_ws,
                        const uint32_t *__restrict__ comb_b, const uint32_t *__restrict__ rec,
-                       CtxCounters *__restrict__ ctr, const uint32_t *__restrict__ miss_list,
+                       RoutedCounters *__restrict__ ctr, const uint32_t *__restrict__ miss_list,
                        const uint32_t *__restrict__ fb_list, uint32_t *__restrict__ canary, uint32_t nonce,
                        uint32_t inject, uint32_t *__restrict__ fault, uint64_t *__restrict__ totals) {
   constexpr int kEnt = (1 << (WA - 1)) + 1;
@@ -542,10 +528,7 @@ hsv_ctx_generic_kernel(const uint8_t *__restrict__ records, uint32_t n, uint8_t 
       load_triple(records, 128, records + 32, 128, records + 96, 128, idx, pkw, sigw, msgw);
       const uint32_t f = verify_one_full_comb<WA, false, CB>(pkw, sigw, msgw, comb_b, vt);
       bad |= ((f & kFault) ? 1u : 0u) | (canary[slot] != nonce ? 2u : 0u);
-      if (valid) {
-        if (flags_out) flags_out[idx] = (uint8_t)f;
-        if (strict_bits && (f & kStrictOk)) atomicOr(&strict_bits[idx >> 5], 1u << (idx & 31u));
-      }
+      if (valid) store_verdict(flags_out, strict_bits, idx, f);
       continue;
     }
     const uint32_t b0 = base - fb_end;
@@ -564,10 +547,7 @@ hsv_ctx_generic_kernel(const uint8_t *__restrict__ records, uint32_t n, uint8_t 
     const bool own = valid && !(meta & kPrepFallback);
     const uint32_t f = verify_one_prepped<WA, CB>(pkw, rw, rec + li, n, meta, comb_b, vt);
     bad |= ((f & kFault) ? 1u : 0u) | (canary[slot] != nonce ? 2u : 0u);
-    if (own) {
-      if (flags_out) flags_out[li] = (uint8_t)f;
-      if (strict_bits && (f & kStrictOk)) atomicOr(&strict_bits[li >> 5], 1u << (li & 31u));
-    }
+    if (own) store_verdict(flags_out, strict_bits, li, f);
   }
   report_faults(fault, bad);
 }
@@ -636,44 +616,10 @@ extern "C" hipError_t hsv_launch_tx_fused(uint32_t grid, const uint8_t *txs, con
 }
 
 // ---- one round of hsv_committee_verify_transactions* -------------------------------
-namespace {
-// blocks per CU of the two persistent passes and the device's CUs, cached per device
-struct CtxGrids {
-  int comb_bpc, generic_bpc, cus;
-  int comb4_bpc;  // the compact comb pass, from its own occupancy query
-};
-hipError_t ctx_grids(int dev, CtxGrids *out) {
-  static std::mutex mu;
-  static std::unordered_map<int, CtxGrids> per_dev;
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = per_dev.find(dev);
-  if (it == per_dev.end()) {
-    int bc = 0, bc4 = 0, bg = 0, cus = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &bc, reinterpret_cast<const void *>(hsv::hsv_ctx_comb_kernel), 256, 0);
-    if (e == hipSuccess)
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-          &bc4, reinterpret_cast<const void *>(hsv::hsv_ctx_comb4_kernel), 256, 0);
-    if (e == hipSuccess)
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-          &bg, reinterpret_cast<const void *>(hsv::hsv_ctx_generic_kernel<4, HSV_HP_WAVES, 16>), hsv::kBlock, 0);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return e;
-    it = per_dev.emplace(dev, CtxGrids{std::max(1, bc), std::max(1, bg), std::max(1, cus), std::max(1, bc4)}).first;
-  }
-  *out = it->second;
-  return hipSuccess;
-}
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-}  // namespace
-
-// n <= 2^22 transactions (current device, no synchronisation): counters and
-// strict words zeroed on the stream, then the route kernel, the comb pass and
-// the generic pass.  Both persistent grids fit the device at once (occupancy x
-// CUs, one CU left free once the resident service has run, as launch_hp) and
-// are capped by ceil(n / 256): the host knows n, not the split.  Workspace
-// from the library pool: per-lane tables | counters | canaries | records |
-// hit list | miss list | fallback list | prepass words.
+// n <= 2^22 transactions: the round of hsv_routed.hpp (RoutedRound: grids,
+// memsets, the comb pass by table width).  Workspace from the library pool:
+// per-lane tables | counters | canaries | records | hit list | miss list |
+// fallback list | prepass words.
 extern "C" hipError_t hsv_launch_committee_tx(const uint8_t *txs, const uint64_t *offsets, uint64_t tx_size, uint32_t n,
                                               const uint32_t *keytab, uint32_t keymask, uint64_t seed,
                                               const uint8_t *pks, const uint8_t *key_flags, uint32_t nkeys,
@@ -684,54 +630,41 @@ extern "C" hipError_t hsv_launch_committee_tx(const uint8_t *txs, const uint64_t
   if (n == 0) return hipSuccess;
   if (n > (1u << 22) || (digit_bits != 8 && digit_bits != 4) || !btable || !comb16 || !fault || (nkeys && (!keytab || !pks || !key_flags || !key_tables)))
     return hipErrorInvalidValue;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  hsv::RoutedRound r;
+  hipError_t e = r.size(n, digit_bits, reinterpret_cast<const void *>(hsv::hsv_ctx_comb_kernel),
+                        reinterpret_cast<const void *>(hsv::hsv_ctx_comb4_kernel),
+                        reinterpret_cast<const void *>(hsv::hsv_ctx_generic_kernel<4, HSV_HP_WAVES, 16>));
   if (e != hipSuccess) return e;
-  CtxGrids g;
-  e = ctx_grids(dev, &g);
-  if (e != hipSuccess) return e;
-  const int cus = hsvi_resident_started() && g.cus > 1 ? g.cus - 1 : g.cus;
-  const uint32_t blocks_needed = (n + hsv::kBlock - 1) / hsv::kBlock;
-  const uint32_t grid_c =
-      std::min<uint32_t>(blocks_needed, (uint32_t)((digit_bits == 4 ? g.comb4_bpc : g.comb_bpc) * cus));
-  const uint32_t grid_g = std::min<uint32_t>(blocks_needed, (uint32_t)(g.generic_bpc * cus));
-  const size_t vt_bytes = (size_t)grid_g * hsv::kBlock * hsv::vt_lane_uint4<4>() * sizeof(uint4);
-  const size_t canary_bytes = up256((size_t)grid_g * hsv::kBlock * sizeof(uint32_t));
-  const size_t rec_bytes = (size_t)n * 128, hit_bytes = up256((size_t)n * sizeof(uint2));
-  const size_t list_bytes = up256((size_t)n * sizeof(uint32_t));
+  const size_t rec_bytes = (size_t)n * 128, hit_bytes = hsv::up256((size_t)n * sizeof(uint2));
+  const size_t list_bytes = hsv::up256((size_t)n * sizeof(uint32_t));
   const size_t prep_bytes = (size_t)n * hsv::kPrepWords * sizeof(uint32_t);
-  const size_t need = vt_bytes + 256 + canary_bytes + rec_bytes + hit_bytes + 2 * list_bytes + prep_bytes;
-  hsv::Workspace ws(nullptr, 0, need, stream);
+  hsv::Workspace ws(nullptr, 0, r.head_bytes() + rec_bytes + hit_bytes + 2 * list_bytes + prep_bytes, stream);
   if (ws.status() != hipSuccess) return ws.status();
   uint8_t *p = ws.get();
   uint4 *vt_ws = reinterpret_cast<uint4 *>(p);
-  hsv::CtxCounters *ctr = reinterpret_cast<hsv::CtxCounters *>(p += vt_bytes);
+  hsv::RoutedCounters *ctr = reinterpret_cast<hsv::RoutedCounters *>(p += r.vt_bytes);
   uint32_t *canary = reinterpret_cast<uint32_t *>(p += 256);
-  uint8_t *records = (p += canary_bytes);
+  uint8_t *records = (p += r.canary_bytes);
   uint2 *hit_list = reinterpret_cast<uint2 *>(p += rec_bytes);
   uint32_t *miss_list = reinterpret_cast<uint32_t *>(p += hit_bytes);
   uint32_t *fb_list = reinterpret_cast<uint32_t *>(p += list_bytes);
   uint32_t *prep = reinterpret_cast<uint32_t *>(p += list_bytes);
   const uint32_t inject = (uint32_t)hsvi_inject_mode();
-  e = hipMemsetAsync(ctr, 0, sizeof(hsv::CtxCounters), stream);
-  if (e == hipSuccess && strict_bits) e = hipMemsetAsync(strict_bits, 0, (size_t)((n + 31u) / 32u) * 4u, stream);
+  e = hsv::RoutedRound::zero(ctr, strict_bits, n, stream);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(hsv::hsv_ctx_route_kernel, dim3(blocks_needed), dim3(hsv::kTxBlock), 0, stream, txs, offsets,
+    hipLaunchKernelGGL(hsv::hsv_ctx_route_kernel, dim3(r.blocks_needed), dim3(hsv::kTxBlock), 0, stream, txs, offsets,
                        tx_size, n, reinterpret_cast<uint4 *>(records), keytab, keymask, seed, pks, nkeys, ctr, hit_list,
                        miss_list, prep, fb_list, hsvi_lattice_bits(), flags_out);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) {  // the committee's table width decides the comb pass, nothing else
-    if (digit_bits == 4)
-      hipLaunchKernelGGL(hsv::hsv_ctx_comb4_kernel, dim3(grid_c), dim3(256), 0, stream, records, n, ctr, hit_list, pks,
-                         key_flags, nkeys, key_tables, comb16, flags_out, strict_bits, inject, fault);
-    else
-      hipLaunchKernelGGL(hsv::hsv_ctx_comb_kernel, dim3(grid_c), dim3(256), 0, stream, records, n, ctr, hit_list, pks,
-                         key_flags, nkeys, key_tables, btable, flags_out, strict_bits, inject, fault);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(r.pick(hsv::hsv_ctx_comb_kernel, hsv::hsv_ctx_comb4_kernel), dim3(r.grid_c), dim3(256), 0,
+                       stream, records, n, ctr, hit_list, pks, key_flags, nkeys, key_tables, r.pick(btable, comb16),
+                       flags_out, strict_bits, inject, fault);
     e = hipGetLastError();
   }
   if (e == hipSuccess) {
-    hipLaunchKernelGGL((hsv::hsv_ctx_generic_kernel<4, HSV_HP_WAVES, 16>), dim3(grid_g), dim3(hsv::kBlock), 0, stream,
+    hipLaunchKernelGGL((hsv::hsv_ctx_generic_kernel<4, HSV_HP_WAVES, 16>), dim3(r.grid_g), dim3(hsv::kBlock), 0, stream,
                        records, n, flags_out, strict_bits, vt_ws, comb16, prep, ctr, miss_list, fb_list, canary,
                        hsvi_next_nonce(), inject, fault, totals);
     e = hipGetLastError();
