@@ -1,12 +1,16 @@
 // Host-side state shared by the C-ABI translation units (hsv_capi.cpp,
-// hsv_committee_api.cpp, hsv_tx.cpp, hsv_msgs_api.cpp, hsv_signer_api.cpp,
-// hsv_numa.cpp) and hsv_test_hooks.cpp.  Not part of the public ABI.
+// hsv_committee_api.cpp, hsv_resident.cpp, hsv_auto_committee.cpp, hsv_tx.cpp,
+// hsv_msgs_api.cpp, hsv_signer_api.cpp, hsv_numa.cpp) and hsv_test_hooks.cpp.
+// Not part of the public ABI.  What only the three committee units share is in
+// hsv_committee_host.h.
 //
 // The call layer every entry-point family is built from:
 //   * BatchSpan (hsv_batch.hpp): the chunk walk of a ragged or fixed-size host
 //     batch, a chunk's geometry and the length check;
 //   * StagedBlock: one pool block with aligned regions and the self-check
-//     words, drained by finish() -- the staged host forms;
+//     words, drained by finish() -- the staged host forms of the message
+//     calls, which are one walk (staged_msgs_host), as those of the
+//     transaction calls are (staged_tx_host);
 //   * DeviceCall: device, guard, B table and fault words of a stream-ordered
 //     device-form call.
 //
@@ -72,15 +76,23 @@ inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 constexpr size_t kStageBytes = size_t(1) << 29;
 inline std::atomic<size_t> g_stage_bytes{kStageBytes};
 
-// Inputs a kernel reads straight from pinned memory (the zero-copy latency
-// form) are written with streaming stores, so they sit in DRAM and not in the
-// writing core's cache: the GPU's reads then need no snoop of a remote core's
-// cache, whose cost grows with the distance from that core to the PCIe root
-// (after a host load had moved the calling thread, the C3 QC read 0.0634
-// against 0.0543 ms, profiles/r05q_idle.txt).  dst 16-byte aligned; the tail
-// of n that is not a multiple of 16 is a plain copy.  stage_fence() orders the
-// streaming stores before the launch that reads them.
-inline void stage_copy(uint8_t *dst, const void *src, size_t n) {
+// The two copies into pinned staging.
+//   * stage_stream: streaming stores, so the bytes sit in DRAM and not in the
+//     writing core's cache: the GPU's reads of a zero-copy launch then need no
+//     snoop of a remote core's cache, whose cost grows with the distance from
+//     that core to the PCIe root (after a host load had moved the calling
+//     thread, the C3 QC read 0.0634 against 0.0543 ms, profiles/r05q_idle.txt).
+//     dst 16-byte aligned; the tail of n that is not a multiple of 16 is a
+//     plain copy.  stage_fence() orders the streaming stores before the launch
+//     that reads them.
+//   * stage_copy (hsv_capi.cpp, declared below): a cached memcpy below 64 KiB,
+//     non-temporal stores from there on, split over the pack pool above 1 MiB.
+// Only committee_run's key_idx copy is a stage_stream.  Its signature and
+// message copies, run_on_device's pack and the transaction walk are
+// stage_copy: until the two had names of their own they were overloads of one,
+// told apart by the source pointer's type, and those sites' const uint8_t *
+// sources always took this one.
+inline void stage_stream(uint8_t *dst, const void *src, size_t n) {
   const uint8_t *s = static_cast<const uint8_t *>(src);
 #if defined(__SSE2__)
   size_t i = 0;
@@ -264,8 +276,9 @@ int ensure_btable(DevCtx &c);
 int ensure_btable16(DevCtx &c);
 int comb_table_for(DevCtx &c, int variant, const uint32_t **out);
 
-// memcpy into pinned staging; large copies split over the pack pool of the
-// current device (its helpers run on the GPU's NUMA node)
+// memcpy into pinned staging (cached below 64 KiB, see stage_stream above);
+// large copies split over the pack pool of the current device (its helpers run
+// on the GPU's NUMA node)
 void stage_copy(uint8_t *dst, const uint8_t *src, size_t bytes);
 
 // ---- host placement (hsv_numa.cpp) -------------------------------------------
@@ -324,13 +337,13 @@ class DeviceCall {
 // ---- hooks shared with hsv_test_hooks.cpp (exported by libhsv_test.so only) ----
 int auto_committee_corrupt_tables();  // zero the cached tables of the automatic committee
 
-// ---- the automatic committee cache (hsv_committee_api.cpp) --------------------
+// ---- the automatic committee cache (hsv_auto_committee.cpp) -------------------
 // Strict verification of small batches whose keys are all cached: HSV_OK
 // when done, 1 when the caller should take the generic path, < 0 on error.
 int auto_committee_try(const uint8_t *pk, const uint8_t *sig, const uint8_t *msg, size_t msg_stride, size_t n,
                        uint8_t *flags_out);
 void auto_committee_shutdown();
-// resident latency service (on by default, hsv_committee_api.cpp)
+// resident latency service (on by default, hsv_resident.cpp)
 // A scope in which its kernel does not run: stopped at construction, and no
 // request or relaunch until destruction (small calls launch meanwhile).  Held
 // around every hipFree / hipHostFree of the library -- they wait for every
@@ -359,5 +372,46 @@ int batch_verdict(const uint8_t *flags, size_t n);
 // The length check of the transaction host forms (hsv_tx.cpp): HSV_OK, or
 // HSV_ERR_INVALID_ARG naming the first transaction shorter than 96 bytes.
 int tx_lengths_ok(const uint64_t *offsets, size_t tx_size, size_t n);
+
+// ---- the staged host forms and the argument checks of the generic calls and
+// ---- their committee twins (hsv_tx.cpp, hsv_msgs_api.cpp) ----------------------
+// A step run once on the slot's stream after slot_prepare (the committee's
+// counts_begin), or none.
+using StagedBegin = std::function<int(hipStream_t)>;
+
+// Transactions [lo, hi) of the caller's arrays through a slot of device c
+// (current, its tables ensured by the caller), chunk by chunk: at most kChunk
+// items and g_stage_bytes bytes per launch.  Per chunk one H2D copy, the
+// memset of flags and self-check words, `launch` on the chunk in HBM (d_rec:
+// rec_bytes per item, 128 for the generic kernels' records, 0 = no region),
+// the D2H, the drain, check_faults under `where`, the copy out.
+using TxLaunch = std::function<int(const uint8_t *d_txs, const uint64_t *d_offsets, size_t m, uint8_t *d_rec,
+                                   uint8_t *d_flags, uint32_t *d_fault, hipStream_t stream)>;
+int staged_tx_host(DevCtx &c, const uint8_t *txs, const uint64_t *offsets, size_t tx_size, size_t lo, size_t hi,
+                   uint8_t *flags_out, size_t rec_bytes, const StagedBegin &begin, const TxLaunch &launch,
+                   const char *where);
+// "no output", and the length check of a fixed size, of the two
+// *_verify_transactions_device calls
+int tx_device_args_ok(const uint64_t *d_offsets, size_t tx_size, const uint8_t *d_flags,
+                      const uint32_t *d_strict_bits);
+
+// n whole messages through a slot of device c and one StagedBlock per launch
+// (flags | pk | sig | offsets rebased to the chunk | message bytes): at most
+// kChunk items and g_stage_bytes message bytes per launch.  `tables` ensures
+// the B tables `launch` reads (current device c.device); alloc_what and
+// finish_where are the caller's texts for hsv_last_error.
+using MsgsLaunch = std::function<hipError_t(const uint8_t *d_pk, const uint8_t *d_sig, const uint8_t *d_msgs,
+                                            const uint64_t *d_offsets, size_t m, uint8_t *d_flags, uint32_t *d_fault,
+                                            hipStream_t stream)>;
+int staged_msgs_host(DevCtx &c, const std::function<int()> &tables, const StagedBegin &begin,
+                     const MsgsLaunch &launch, const char *alloc_what, const char *finish_where, const uint8_t *pk,
+                     const uint8_t *sig, const uint8_t *msgs, const uint64_t *offsets, size_t msg_len,
+                     size_t msg_stride, size_t n, uint8_t *flags_out);
+// the checks of the two *_verify_msgs host calls after their null test ...
+int msgs_host_args_ok(const uint8_t *msgs, const uint64_t *offsets, size_t msg_len, size_t msg_stride, size_t n);
+// ... and of the two device calls from "null d_msgs" on
+int msgs_device_args_ok(const uint8_t *d_pk, size_t pk_stride, const uint8_t *d_sig, size_t sig_stride,
+                        const uint8_t *d_msgs, const uint64_t *d_offsets, size_t msg_len, size_t msg_stride,
+                        const uint8_t *d_flags, const uint32_t *d_strict_bits);
 
 }  // namespace hsvh

@@ -20,7 +20,7 @@ extern "C" {
 hipError_t hsv_ws_malloc(void **p, size_t bytes, hipStream_t stream);
 void hsv_ws_trim(void);  // hsv_shutdown: release the pools' free blocks
 
-// The resident latency service (hsv_committee_api.cpp) from the kernel
+// The resident latency service (hsv_resident.cpp) from the kernel
 // launchers: pause (on = 1) / resume (on = 0) it around a device-wide wait,
 // as hsvh::ResidentPause; hsvi_resident_started() is 1 once its block has run
 // in this process with the service on -- the persistent point pass then

@@ -5,7 +5,7 @@
 //
 // A transaction carries its signer's 32 raw key bytes; whether they are a
 // committee member's decides which kernels verify it.  The table is the
-// device form of KeyIndex (hsv_committee_api.cpp): open addressing in HBM,
+// device form of KeyIndex (hsv_keyindex.hpp): open addressing in HBM,
 // capacity a power of two >= 2 x keys, linear probing, slot = 1 + member
 // index, 0 = empty.  A probe compares all 32 bytes against the committee's key
 // array (d_pks, 32 bytes per member), so a hit is exact; of a key listed twice
@@ -28,7 +28,8 @@ namespace hsv {
 
 constexpr uint32_t kKeytabMiss = 0xffffffffu;
 
-// KeyHash (hsv_committee_api.cpp) over the key's eight little-endian words
+// the keyed mix, also KeyHash's (hsv_keyindex.hpp), over the key's eight
+// little-endian words
 HSV_INL uint64_t keytab_hash(uint64_t seed, const uint32_t pkw[8]) {
   uint64_t h = seed;
   for (int i = 0; i < 4; ++i) {

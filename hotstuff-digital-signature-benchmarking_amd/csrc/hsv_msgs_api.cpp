@@ -5,6 +5,7 @@
 // message prepass) and the point pass of csrc/hsv_kernels.hip.  The host form
 // is plain staged copies on one device: no pipelining, no multi-GPU sharding.
 #include <algorithm>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -33,13 +34,25 @@ hipError_t msgs_chunks(const uint8_t *d_pk, size_t pk_stride, const uint8_t *d_s
 
 }  // namespace
 
-extern "C" {
+namespace hsvh {
 
-int hsv_verify_msgs_device(const uint8_t *d_pk, size_t pk_stride, const uint8_t *d_sig, size_t sig_stride,
-                           const uint8_t *d_msgs, const uint64_t *d_offsets, size_t msg_len, size_t msg_stride,
-                           size_t n, uint8_t *d_flags, uint32_t *d_strict_bits, uint32_t *d_fault, void *stream) {
-  if (n == 0) return HSV_OK;
-  if (!d_pk || !d_sig) return fail(HSV_ERR_INVALID_ARG, "null input pointer");
+int msgs_host_args_ok(const uint8_t *msgs, const uint64_t *offsets, size_t msg_len, size_t msg_stride, size_t n) {
+  if (n > 0xffffffffu) return fail(HSV_ERR_INVALID_ARG, "batch too large");
+  bool any_bytes = msg_len != 0;
+  if (offsets) {
+    const size_t bad = first_bad_item(offsets, n, 0);
+    if (bad != n) return fail(HSV_ERR_INVALID_ARG, "offsets decrease at message " + std::to_string(bad));
+    any_bytes = offsets[n] != offsets[0];
+  } else if (msg_stride != 0 && msg_stride < msg_len) {
+    return fail(HSV_ERR_INVALID_ARG, "messages overlap");
+  }
+  if (any_bytes && !msgs) return fail(HSV_ERR_INVALID_ARG, "null msgs");
+  return HSV_OK;
+}
+
+int msgs_device_args_ok(const uint8_t *d_pk, size_t pk_stride, const uint8_t *d_sig, size_t sig_stride,
+                        const uint8_t *d_msgs, const uint64_t *d_offsets, size_t msg_len, size_t msg_stride,
+                        const uint8_t *d_flags, const uint32_t *d_strict_bits) {
   if (!d_msgs && (d_offsets || msg_len)) return fail(HSV_ERR_INVALID_ARG, "null d_msgs");
   if (!d_flags && !d_strict_bits) return fail(HSV_ERR_INVALID_ARG, "no output");
   const uintptr_t mis =
@@ -48,8 +61,69 @@ int hsv_verify_msgs_device(const uint8_t *d_pk, size_t pk_stride, const uint8_t 
   if (reinterpret_cast<uintptr_t>(d_offsets) & 7u) return fail(HSV_ERR_ALIGN, "d_offsets must be 8-byte aligned");
   if (pk_stride < 32 || sig_stride < 64) return fail(HSV_ERR_INVALID_ARG, "record strides overlap");
   if (!d_offsets && msg_stride != 0 && msg_stride < msg_len) return fail(HSV_ERR_INVALID_ARG, "messages overlap");
+  return HSV_OK;
+}
+
+// The one walk of the staged message host forms (hsv_host.h).
+int staged_msgs_host(DevCtx &c, const std::function<int()> &tables, const StagedBegin &begin,
+                     const MsgsLaunch &launch, const char *alloc_what, const char *finish_where, const uint8_t *pk,
+                     const uint8_t *sig, const uint8_t *msgs, const uint64_t *offsets, size_t msg_len,
+                     size_t msg_stride, size_t n, uint8_t *flags_out) {
+  DeviceGuard guard(c.device);
+  if (guard.status() != hipSuccess) return hip_fail("hipSetDevice", guard.status());
+  int rc = tables();
+  if (rc != HSV_OK) return rc;
+  SlotLease lease(c);
+  Slot &slot = lease.slot();
+  rc = slot_prepare(slot, 0, 0);
+  if (rc != HSV_OK) return rc;
+  hipStream_t st = slot.stream;
+  if (begin) rc = begin(st);
+  if (rc != HSV_OK) return rc;
+  const BatchSpan span{offsets, msg_stride, msg_len};
+  std::vector<uint64_t> rel;  // a chunk's offsets, relative to its first byte
+  for (size_t a = 0, b; a < n; a = b) {
+    b = span.chunk_end(a, n, kChunk, g_stage_bytes.load());
+    const size_t m = b - a, bytes = span.span_bytes(a, b);
+    StagedBlock blk(st);
+    const size_t off_flags = blk.add(m), off_pk = blk.add(m * 32), off_sig = blk.add(m * 64);
+    const size_t off_offs = blk.add(offsets ? (m + 1) * 8 : 0), off_msg = blk.add(bytes);
+    // unwritten flags read as rejections
+    rc = blk.alloc(alloc_what, m);
+    if (rc != HSV_OK) return rc;
+    blk.in(off_pk, pk + a * 32, m * 32);
+    blk.in(off_sig, sig + a * 64, m * 64);
+    if (offsets) {
+      rel.resize(m + 1);
+      span.rel_offsets(a, b, rel.data());
+      blk.in(off_offs, rel.data(), (m + 1) * 8);
+    }
+    blk.in(off_msg, msgs + span.first_byte(a), bytes);
+    if (blk.ok())
+      blk.step(launch(blk.at(off_pk), blk.at(off_sig), blk.at(off_msg),
+                      offsets ? reinterpret_cast<uint64_t *>(blk.at(off_offs)) : nullptr, m, blk.at(off_flags),
+                      blk.fault(), st));
+    blk.out(flags_out + a, off_flags, m);
+    rc = blk.finish(finish_where);
+    if (rc != HSV_OK) return rc;
+  }
+  return HSV_OK;
+}
+
+}  // namespace hsvh
+
+extern "C" {
+
+int hsv_verify_msgs_device(const uint8_t *d_pk, size_t pk_stride, const uint8_t *d_sig, size_t sig_stride,
+                           const uint8_t *d_msgs, const uint64_t *d_offsets, size_t msg_len, size_t msg_stride,
+                           size_t n, uint8_t *d_flags, uint32_t *d_strict_bits, uint32_t *d_fault, void *stream) {
+  if (n == 0) return HSV_OK;
+  if (!d_pk || !d_sig) return fail(HSV_ERR_INVALID_ARG, "null input pointer");
+  int rc = msgs_device_args_ok(d_pk, pk_stride, d_sig, sig_stride, d_msgs, d_offsets, msg_len, msg_stride, d_flags,
+                               d_strict_bits);
+  if (rc != HSV_OK) return rc;
   DeviceCall call;
-  const int rc = call.begin(d_pk, stream, d_fault, DeviceCall::kWide);
+  rc = call.begin(d_pk, stream, d_fault, DeviceCall::kWide);
   if (rc != HSV_OK) return rc;
   const hipError_t e = msgs_chunks(d_pk, pk_stride, d_sig, sig_stride, d_msgs, d_offsets, msg_len, msg_stride, n,
                                    d_flags, d_strict_bits, call.comb, call.fault, call.stream);
@@ -61,57 +135,20 @@ int hsv_verify_msgs(const uint8_t *pk, const uint8_t *sig, const uint8_t *msgs, 
   CallScope call;
   if (n == 0) return HSV_OK;
   if (!pk || !sig || !flags_out) return fail(HSV_ERR_INVALID_ARG, "null pointer");
-  if (n > 0xffffffffu) return fail(HSV_ERR_INVALID_ARG, "batch too large");
-  bool any_bytes = msg_len != 0;
-  if (offsets) {
-    const size_t bad = first_bad_item(offsets, n, 0);
-    if (bad != n) return fail(HSV_ERR_INVALID_ARG, "offsets decrease at message " + std::to_string(bad));
-    any_bytes = offsets[n] != offsets[0];
-  } else if (msg_stride != 0 && msg_stride < msg_len) {
-    return fail(HSV_ERR_INVALID_ARG, "messages overlap");
-  }
-  if (any_bytes && !msgs) return fail(HSV_ERR_INVALID_ARG, "null msgs");
-  int rc = ensure_init();
+  int rc = msgs_host_args_ok(msgs, offsets, msg_len, msg_stride, n);
+  if (rc != HSV_OK) return rc;
+  rc = ensure_init();
   if (rc != HSV_OK) return rc;
   DevCtx &c = ctx(home_device());
-  DeviceGuard guard(c.device);
-  if (guard.status() != hipSuccess) return hip_fail("hipSetDevice", guard.status());
-  rc = ensure_btable16(c);
-  if (rc != HSV_OK) return rc;
-  SlotLease lease(c);
-  Slot &slot = lease.slot();
-  rc = slot_prepare(slot, 0, 0);
-  if (rc != HSV_OK) return rc;
-  hipStream_t st = slot.stream;
-  const BatchSpan span{offsets, msg_stride, msg_len};
-  std::vector<uint64_t> rel;  // a chunk's offsets, relative to its first byte
-  for (size_t a = 0, b; a < n; a = b) {
-    b = span.chunk_end(a, n, kChunk, g_stage_bytes.load());
-    const size_t m = b - a, bytes = span.span_bytes(a, b);
-    StagedBlock blk(st);
-    const size_t off_flags = blk.add(m), off_pk = blk.add(m * 32), off_sig = blk.add(m * 64);
-    const size_t off_offs = blk.add(offsets ? (m + 1) * 8 : 0), off_msg = blk.add(bytes);
-    // unwritten flags read as rejections
-    rc = blk.alloc("allocating the message verification buffers", m);
-    if (rc != HSV_OK) return rc;
-    blk.in(off_pk, pk + a * 32, m * 32);
-    blk.in(off_sig, sig + a * 64, m * 64);
-    if (offsets) {
-      rel.resize(m + 1);
-      span.rel_offsets(a, b, rel.data());
-      blk.in(off_offs, rel.data(), (m + 1) * 8);
-    }
-    blk.in(off_msg, msgs + span.first_byte(a), bytes);
-    if (blk.ok())
-      blk.step(hsv_launch_verify_msgs(blk.at(off_pk), 32, blk.at(off_sig), 64, blk.at(off_msg),
-                                      offsets ? reinterpret_cast<uint64_t *>(blk.at(off_offs)) : nullptr, msg_len,
-                                      msg_stride, (uint32_t)m, blk.at(off_flags), nullptr, c.d_btable16, blk.fault(),
-                                      st));
-    blk.out(flags_out + a, off_flags, m);
-    rc = blk.finish("hsv_verify_msgs");
-    if (rc != HSV_OK) return rc;
-  }
-  return HSV_OK;
+  return staged_msgs_host(
+      c, [&] { return ensure_btable16(c); }, nullptr,
+      [&](const uint8_t *d_pk, const uint8_t *d_sig, const uint8_t *d_msgs, const uint64_t *d_offsets, size_t m,
+          uint8_t *d_flags, uint32_t *d_fault, hipStream_t st) {
+        return hsv_launch_verify_msgs(d_pk, 32, d_sig, 64, d_msgs, d_offsets, msg_len, msg_stride, (uint32_t)m,
+                                      d_flags, nullptr, c.d_btable16, d_fault, st);
+      },
+      "allocating the message verification buffers", "hsv_verify_msgs", pk, sig, msgs, offsets, msg_len, msg_stride,
+      n, flags_out);
 }
 
 }  // extern "C"

@@ -41,11 +41,13 @@ int tx_lengths_ok(const uint64_t *offsets, size_t tx_size, size_t n) {
                   : fail(HSV_ERR_INVALID_ARG, "transaction " + std::to_string(bad) + " is shorter than 96 bytes");
 }
 
-namespace {
-
-// transactions [lo, hi) of the caller's arrays on device c, chunk by chunk
-int run_tx_on_device(DevCtx &c, const uint8_t *txs, const uint64_t *offsets, size_t tx_size, size_t lo, size_t hi,
-                     uint8_t *flags_out) {
+// The one walk of the staged transaction host forms (hsv_host.h).  With
+// rec_bytes = 0 the record region is empty and the device and host layouts
+// coincide: byte for byte the layout the committee form had while it was a
+// copy of this walk (tx bytes | offsets | flags | self-check words).
+int staged_tx_host(DevCtx &c, const uint8_t *txs, const uint64_t *offsets, size_t tx_size, size_t lo, size_t hi,
+                   uint8_t *flags_out, size_t rec_bytes, const StagedBegin &begin, const TxLaunch &launch,
+                   const char *where) {
   const BatchSpan span{offsets, tx_size, tx_size};
   std::vector<size_t> ends;  // the chunks' ends, in order from lo
   size_t max_items = 0, max_bytes = 0;
@@ -58,21 +60,16 @@ int run_tx_on_device(DevCtx &c, const uint8_t *txs, const uint64_t *offsets, siz
   // host: tx bytes | offsets | flags | self-check words
   const size_t off_off = round_up(max_bytes, kAlign);
   const size_t rec_off = off_off + round_up((max_items + 1) * 8, kAlign);
-  const size_t flag_off = rec_off + round_up(max_items * 128, kAlign);
+  const size_t flag_off = rec_off + round_up(max_items * rec_bytes, kAlign);
   const size_t fault_off = flag_off + round_up(max_items, kAlign);
   const size_t d_total = fault_off + kAlign;
   const size_t h_flag_off = rec_off;
   const size_t h_fault_off = h_flag_off + round_up(max_items, kAlign);
   const size_t h_total = h_fault_off + kAlign;
-  DeviceGuard guard(c.device);
-  if (guard.status() != hipSuccess) return hip_fail("hipSetDevice", guard.status());
-  const int v = variant();
-  const uint32_t *comb_b = nullptr;
-  int rc = comb_table_for(c, v, &comb_b);
-  if (rc != HSV_OK) return rc;
   SlotLease lease(c);
   Slot &s = lease.slot();
-  rc = slot_prepare(s, d_total, h_total);
+  int rc = slot_prepare(s, d_total, h_total);
+  if (rc == HSV_OK && begin) rc = begin(s.stream);
   if (rc != HSV_OK) return rc;
   size_t a = lo;
   for (const size_t b : ends) {
@@ -91,9 +88,8 @@ int run_tx_on_device(DevCtx &c, const uint8_t *txs, const uint64_t *offsets, siz
       (void)hipStreamSynchronize(s.stream);
       return hip_fail("hipMemcpyAsync H2D", e);
     }
-    rc = tx_enqueue(v, comb_b, s.d_buf, offsets ? reinterpret_cast<const uint64_t *>(s.d_buf + off_off) : nullptr,
-                    tx_size, m, s.d_buf + rec_off, s.d_buf + flag_off, nullptr,
-                    reinterpret_cast<uint32_t *>(s.d_buf + fault_off), s.stream);
+    rc = launch(s.d_buf, offsets ? reinterpret_cast<const uint64_t *>(s.d_buf + off_off) : nullptr, m,
+                s.d_buf + rec_off, s.d_buf + flag_off, reinterpret_cast<uint32_t *>(s.d_buf + fault_off), s.stream);
     if (rc == HSV_OK) {
       e = hipMemcpyAsync(h + h_flag_off, s.d_buf + flag_off, fault_off + kFaultBytes - flag_off,
                          hipMemcpyDeviceToHost, s.stream);
@@ -102,12 +98,40 @@ int run_tx_on_device(DevCtx &c, const uint8_t *txs, const uint64_t *offsets, siz
     e = hipStreamSynchronize(s.stream);  // nothing of this call stays in flight
     if (rc != HSV_OK) return rc;
     if (e != hipSuccess) return hip_fail("hipStreamSynchronize", e);
-    rc = check_faults(h + h_fault_off, "transaction verify");
+    rc = check_faults(h + h_fault_off, where);
     if (rc != HSV_OK) return rc;
     std::memcpy(flags_out + (a - lo), h + h_flag_off, m);
     a = b;
   }
   return HSV_OK;
+}
+
+int tx_device_args_ok(const uint64_t *d_offsets, size_t tx_size, const uint8_t *d_flags,
+                      const uint32_t *d_strict_bits) {
+  if (!d_flags && !d_strict_bits) return fail(HSV_ERR_INVALID_ARG, "no output");
+  if (!d_offsets && tx_size < 96) return fail(HSV_ERR_INVALID_ARG, "transactions are shorter than 96 bytes");
+  return HSV_OK;
+}
+
+namespace {
+
+// transactions [lo, hi) of the caller's arrays on device c: the generic
+// kernels, with their 128-byte record per item
+int run_tx_on_device(DevCtx &c, const uint8_t *txs, const uint64_t *offsets, size_t tx_size, size_t lo, size_t hi,
+                     uint8_t *flags_out) {
+  DeviceGuard guard(c.device);
+  if (guard.status() != hipSuccess) return hip_fail("hipSetDevice", guard.status());
+  const int v = variant();
+  const uint32_t *comb_b = nullptr;
+  const int rc = comb_table_for(c, v, &comb_b);
+  if (rc != HSV_OK) return rc;
+  return staged_tx_host(
+      c, txs, offsets, tx_size, lo, hi, flags_out, 128, nullptr,
+      [&](const uint8_t *d_txs, const uint64_t *d_offsets, size_t m, uint8_t *d_rec, uint8_t *d_flags,
+          uint32_t *d_fault, hipStream_t s) {
+        return tx_enqueue(v, comb_b, d_txs, d_offsets, tx_size, m, d_rec, d_flags, nullptr, d_fault, s);
+      },
+      "transaction verify");
 }
 
 int run_tx_host(const uint8_t *txs, const uint64_t *offsets, size_t tx_size, size_t n, uint8_t *flags_out) {
@@ -148,10 +172,10 @@ int hsv_verify_transactions_device(const uint8_t *d_txs, const uint64_t *d_offse
                                    uint8_t *d_flags, uint32_t *d_strict_bits, uint32_t *d_fault, void *stream) {
   if (n == 0) return HSV_OK;
   if (!d_txs) return fail(HSV_ERR_INVALID_ARG, "null d_txs");
-  if (!d_flags && !d_strict_bits) return fail(HSV_ERR_INVALID_ARG, "no output");
-  if (!d_offsets && tx_size < 96) return fail(HSV_ERR_INVALID_ARG, "transactions are shorter than 96 bytes");
+  int rc = tx_device_args_ok(d_offsets, tx_size, d_flags, d_strict_bits);
+  if (rc != HSV_OK) return rc;
   DeviceCall call;
-  int rc = call.begin(d_txs, stream, d_fault, DeviceCall::kVariant);
+  rc = call.begin(d_txs, stream, d_fault, DeviceCall::kVariant);
   if (rc != HSV_OK) return rc;
   hipStream_t s = call.stream;
   const size_t per = std::min(n, kChunk);

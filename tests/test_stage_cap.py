@@ -7,7 +7,9 @@ items take many launches: every launch after the first starts at its own item,
 key and byte, and a ragged one gets offsets rebased to its first byte
 (csrc/hsv_batch.hpp; the walk itself is checked on the CPU by
 tests/test_batch_host.py).  hsv_verify_msgs' case is in tests/test_verify_msgs.py,
-next to its fixture.
+next to its fixture.  The committee host forms (hsv_committee_verify_transactions,
+hsv_committee_verify_msgs) run the same two walks and take the same inputs
+over many launches here; their list lengths accumulate over a call's launches.
 """
 import contextlib
 
@@ -16,6 +18,7 @@ import pytest
 
 from conftest import oracle_tx_flags
 from test_txsign import FILL, sign_list, sign_rows
+from test_verify_msgs import ragged_over_the_cap
 
 pytestmark = pytest.mark.gpu
 
@@ -61,6 +64,65 @@ def test_verify_fixed_size_transactions_over_many_launches(hsv, oracle_lib, size
     with stage_cap():
         got = mempool.verify_transactions_fixed(w.txs)
     assert (got == exp).all(), np.nonzero(got != exp)[0][:8]
+
+
+# ---- the committee host forms: the same walks, the same inputs ---------------------
+def _committee(keys, compact=False):
+    from hsverify.committee import Committee
+    return Committee(np.ascontiguousarray(keys, np.uint8).reshape(-1, 32), compact=compact)
+
+
+def test_committee_verify_ragged_golden_transactions_over_many_launches(hsv, oracle_lib, tx_golden):
+    """The 47 golden transactions in five launches against every second
+    distinct key: the golden flags, those of mempool.verify_transactions under
+    the same cap, and list lengths summed over the launches."""
+    from hsverify import _testing, mempool
+    txs, want = tx_golden["txs"], tx_golden["flags"]
+    assert len(txs) == 47 and sum(len(t) for t in txs) == 17157
+    pks = [t[-96:-64] for t in txs]
+    half = set(list(dict.fromkeys(pks))[::2])
+    n_half = sum(p in half for p in pks)
+    assert 0 < n_half < 47
+    with stage_cap(), _committee(np.frombuffer(b"".join(sorted(half)), np.uint8)) as c:
+        got = c.verify_transactions(txs)
+        counts = _testing.committee_tx_counts()
+        generic = mempool.verify_transactions(txs)
+    assert (got == want).all(), [(tx_golden["cases"][i], int(got[i]), int(want[i])) for i in np.nonzero(got != want)[0]]
+    assert (got == generic).all()
+    assert counts[:2] == (n_half, 47 - n_half)
+
+
+@pytest.mark.parametrize("compact", [False, True], ids=["full", "compact"])
+@pytest.mark.parametrize("size", [97, 512])
+def test_committee_verify_fixed_size_transactions_over_many_launches(hsv, oracle_lib, size, compact):
+    """257 transactions, 42 or 8 per launch, the first 128 rows' keys the
+    committee."""
+    from hsverify import _testing, synth
+    w = synth.transactions(N, tx_size=size, seed=size, corrupt_frac=0.1)
+    exp = oracle_tx_flags(oracle_lib, w.txs.reshape(-1), tx_size=size, n=N)
+    assert 0 < (exp & 1).sum() < N
+    with stage_cap(), _committee(w.txs[:128, size - 96:size - 64], compact=compact) as c:
+        got = c.verify_transactions_fixed(w.txs)
+        counts = _testing.committee_tx_counts()
+    assert (got == exp).all(), np.nonzero(got != exp)[0][:8]
+    assert counts[0] + counts[1] == N
+
+
+@pytest.mark.parametrize("compact", [False, True], ids=["full", "compact"])
+def test_committee_verify_ragged_msgs_over_many_launches(hsv, oracle_lib, compact):
+    """The 257 ragged messages of test_verify_msgs.py's case, the 5000-byte one
+    alone in its launch, against half of the distinct keys."""
+    from hsverify import _testing, verifier
+    ref = ragged_over_the_cap(oracle_lib)
+    pk, sig, msgs, exp = ref["pk"], ref["sig"], ref["msgs"], ref["exp"]
+    distinct = list(dict.fromkeys(bytes(k) for k in pk))
+    with stage_cap(), _committee(np.frombuffer(b"".join(distinct[::2]), np.uint8), compact=compact) as c:
+        got = c.verify_msgs(pk, sig, msgs)
+        counts = _testing.committee_msgs_counts()
+        generic = verifier.verify_msgs(pk, sig, msgs)
+    assert (got == exp).all(), np.nonzero(got != exp)[0][:8]
+    assert (got == generic).all()
+    assert counts[0] + counts[1] == len(msgs) == N
 
 
 @pytest.fixture(scope="module")

@@ -85,16 +85,45 @@ def run_device(pk, sig, buf, offsets=None, shift=0, msg_len=0, msg_stride=None, 
             fault.cpu().tolist())
 
 
+_REFERENCE = {}   # computed once per process, read-only: tests/test_stage_cap.py shares it
+
+
+def ragged_reference(oracle_lib):
+    """257 ragged items and the oracle's flags."""
+    if "ragged" not in _REFERENCE:
+        pk, sig, msgs, bad = ragged_batch(51, 257)
+        exp = oracle_msgs(oracle_lib, pk, sig, msgs)
+        assert not (exp[bad] & o.STRICT_OK).any() and (exp[~bad] & o.STRICT_OK).all()
+        for a in (pk, sig, exp):
+            a.setflags(write=False)
+        _REFERENCE["ragged"] = {"pk": pk, "sig": sig, "msgs": msgs, "exp": exp}
+    return _REFERENCE["ragged"]
+
+
+def ragged_over_the_cap(oracle_lib):
+    """The same 257 items with item 100 replaced by a valid message of 5000
+    bytes, longer than the lowered staging cap of 4096: it goes alone in its
+    launch."""
+    if "over_the_cap" not in _REFERENCE:
+        ragged = ragged_reference(oracle_lib)
+        at = 100
+        long = np.random.default_rng(57).integers(0, 256, 5000, dtype=np.uint8).tobytes()
+        pk, sig, msgs, exp = ragged["pk"].copy(), ragged["sig"].copy(), list(ragged["msgs"]), ragged["exp"].copy()
+        pk[at:at + 1], sig[at:at + 1] = sign_ragged(np.full((1, 32), 9, np.uint8), [long])
+        msgs[at] = long
+        exp[at] = oracle_msgs(oracle_lib, pk[at:at + 1], sig[at:at + 1], [long])[0]
+        assert exp[at] & o.STRICT_OK and 0 < (exp & o.STRICT_OK).sum() < len(msgs)
+        for a in (pk, sig, exp):
+            a.setflags(write=False)
+        _REFERENCE["over_the_cap"] = {"pk": pk, "sig": sig, "msgs": msgs, "exp": exp}
+    return _REFERENCE["over_the_cap"]
+
+
 @pytest.fixture(scope="module")
 def ragged(hsv, oracle_lib):
     """257 ragged items and the oracle's flags (computed once, read-only);
     the smaller batches are prefixes."""
-    pk, sig, msgs, bad = ragged_batch(51, 257)
-    exp = oracle_msgs(oracle_lib, pk, sig, msgs)
-    assert not (exp[bad] & o.STRICT_OK).any() and (exp[~bad] & o.STRICT_OK).all()
-    for a in (pk, sig, exp):
-        a.setflags(write=False)
-    return {"pk": pk, "sig": sig, "msgs": msgs, "exp": exp}
+    return ragged_reference(oracle_lib)
 
 
 def test_edge_vectors_as_32_byte_messages(hsv, golden):
@@ -341,13 +370,8 @@ def test_host_form_across_its_byte_cap(hsv, oracle_lib, ragged):
     the cap -- goes alone.  Flags equal the oracle's, and those of the same
     call at the product's cap."""
     from hsverify import _testing, verifier
-    at = 100
-    long = np.random.default_rng(57).integers(0, 256, 5000, dtype=np.uint8).tobytes()
-    pk, sig, msgs, exp = ragged["pk"].copy(), ragged["sig"].copy(), list(ragged["msgs"]), ragged["exp"].copy()
-    pk[at:at + 1], sig[at:at + 1] = sign_ragged(np.full((1, 32), 9, np.uint8), [long])
-    msgs[at] = long
-    exp[at] = oracle_msgs(oracle_lib, pk[at:at + 1], sig[at:at + 1], [long])[0]
-    assert exp[at] & o.STRICT_OK and 0 < (exp & o.STRICT_OK).sum() < len(msgs)
+    ref = ragged_over_the_cap(oracle_lib)
+    pk, sig, msgs, exp = ref["pk"], ref["sig"], ref["msgs"], ref["exp"]
     with _testing.test_library() as lib:
         whole = verifier.verify_msgs(pk, sig, msgs)
         assert lib.hsv_test_stage_bytes(4096) == 1 << 29
