@@ -48,7 +48,8 @@ hsv_prep_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const uint8_
   if (idx >= n) return;
   uint32_t pkw[8], sigw[16], msgw[8];
   load_triple(pk, pk_stride, sig, sig_stride, msg, msg_stride, idx, pkw, sigw, msgw);
-  if (prep_scalars<WA>(pkw, sigw, msgw, rec + idx, n, lat_bits)) fb_list[atomicAdd(&ctr->fb_count, 1u)] = idx;
+  if (prep_scalars<WA, PutPlain, pointpass_digit_bits<WA>()>(pkw, sigw, msgw, rec + idx, n, lat_bits))
+    fb_list[atomicAdd(&ctr->fb_count, 1u)] = idx;
 }
 
 // Pass 2: persistent grid, 64-item batches from ctr->next over a virtual
@@ -70,9 +71,9 @@ hsv_verify_hp_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const u
                      const uint32_t *__restrict__ rec, HcCounters *__restrict__ ctr,
                      const uint32_t *__restrict__ fb_list, uint32_t *__restrict__ canary, uint32_t nonce,
                      uint32_t inject, uint32_t *__restrict__ fault) {
-  constexpr int kEnt = (1 << (WA - 1)) + 1;
+  constexpr bool JOINT = joint_pointpass<WA>();
   const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
-  GlobalVarTab<kEnt> vt{vt_ws + (uint64_t)slot * vt_lane_uint4<WA>(), inject};
+  PointPassTab<WA> vt{vt_ws + (uint64_t)slot * pointpass_lane_uint4<WA>(), inject};
   const uint32_t lane = threadIdx.x & 63u;
   canary[slot] = nonce;
   uint32_t bad = 0;
@@ -144,7 +145,7 @@ hsv_verify_hp_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const u
     ++nbw;
     const uint64_t cyc0 = clock64();
     clk[0] = wall_clock64();
-    const uint32_t f = verify_one_prepped<WA, CB>(pkw, rw, rec + li, n, meta, comb_b, vt, clk);
+    const uint32_t f = verify_one_prepped<WA, CB, JOINT>(pkw, rw, rec + li, n, meta, comb_b, vt, clk);
     clk[4] = wall_clock64();
     {  // lanes 0..7 store one word each (one store region keeps the work loop uniform)
       uint64_t v = 1;
@@ -158,7 +159,7 @@ hsv_verify_hp_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const u
       if (lane < 8u && b0 / 64u < kPhaseCap) g_phase_clk[(uint64_t)(b0 / 64u) * 8u + lane] = v;
     }
 #else
-    const uint32_t f = verify_one_prepped<WA, CB>(pkw, rw, rec + li, n, meta, comb_b, vt);
+    const uint32_t f = verify_one_prepped<WA, CB, JOINT>(pkw, rw, rec + li, n, meta, comb_b, vt);
 #endif
     bad |= ((f & kFault) ? 1u : 0u) | (canary[slot] != nonce ? 2u : 0u);
     const uint32_t fo = KREC && (meta & kPrepVoid) ? 0u : f;
@@ -1160,7 +1161,7 @@ hipError_t launch_hp(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, 
   const int resident = bpc * (hsvi_resident_started() && cus > 1 ? cus - 1 : cus);
   const uint32_t blocks_needed = (n + hsv::kBlock - 1) / hsv::kBlock;
   const uint32_t grid = std::min<uint32_t>(blocks_needed, (uint32_t)resident);
-  const size_t ws_bytes = (size_t)grid * hsv::kBlock * hsv::vt_lane_uint4<WA>() * sizeof(uint4);
+  const size_t ws_bytes = (size_t)grid * hsv::kBlock * hsv::pointpass_lane_uint4<WA>() * sizeof(uint4);
   const size_t canary_bytes = ((size_t)grid * hsv::kBlock * sizeof(uint32_t) + 255) & ~(size_t)255;
   const size_t fb_bytes = (size_t)n * sizeof(uint32_t);
   const size_t rec_bytes = (size_t)n * hsv::kPrepWords * sizeof(uint32_t);
@@ -1190,7 +1191,7 @@ hipError_t launch_hp(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, 
     return ws.done(e);
   }
   if (e == hipSuccess && tx) {
-    static_assert(WA == 4, "hsv_launch_tx_prep writes the WA = 4 prepass record");
+    static_assert(WA == 4, "hsv_launch_tx_prep writes the WA = 4 point pass's prepass record");
     e = hsv_launch_tx_prep(tx->txs, tx->offsets, tx->tx_size, n, tx->records, rec, &ctr->fb_count, fb_list,
                            g_lat_bits.load(), stream);
     pk = tx->records;
@@ -1198,7 +1199,7 @@ hipError_t launch_hp(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, 
     msg = tx->records + 96;
     pk_stride = sig_stride = msg_stride = 128;
   } else if (e == hipSuccess && mp) {
-    static_assert(WA == 4, "hsv_launch_msg_prep writes the WA = 4 prepass record");
+    static_assert(WA == 4, "hsv_launch_msg_prep writes the WA = 4 point pass's prepass record");
     e = hsv_launch_msg_prep(pk, pk_stride, sig, sig_stride, mp->msgs, mp->offsets, mp->msg_len, mp->msg_stride, n,
                             rec, &ctr->fb_count, fb_list, g_lat_bits.load(), stream);
   } else if (e == hipSuccess) {

@@ -176,7 +176,7 @@ __device__ __forceinline__ void tx_record_lane(const uint8_t *__restrict__ txs, 
     for (int j = 0; j < 8; ++j) out.put(i, j, r);
     if constexpr (PREP) {
       // pk = r[0..8), R || s = r[8..24), digest = r[24..32)
-      const bool fallback = prep_scalars<4, Put>(r, r + 8, r + 24, prep + i, n, lat_bits);
+      const bool fallback = prep_scalars<4, Put, pointpass_digit_bits<4>()>(r, r + 8, r + 24, prep + i, n, lat_bits);
       if (fallback && i == i_in) Put::u32(fb_list + atomicAdd(fb_count, 1u), i);  // once per transaction
     }
   }
@@ -246,9 +246,8 @@ hsv_verify_tx_fused_kernel(const uint8_t *__restrict__ txs, const uint64_t *__re
                            uint32_t inject, uint32_t *__restrict__ fault) {
   static_assert(kBlock == kTxBlock, "one staging slot per wave");
   __shared__ uint4 stage_all[kBlock / 64][64 * kTxQ];
-  constexpr int kEnt = (1 << (WA - 1)) + 1;
   const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
-  GlobalVarTab<kEnt> vt{vt_ws + (uint64_t)slot * vt_lane_uint4<WA>(), inject};
+  PointPassTab<WA> vt{vt_ws + (uint64_t)slot * pointpass_lane_uint4<WA>(), inject};
   const uint32_t lane = threadIdx.x & 63u;
   uint4 *stage = stage_all[threadIdx.x >> 6];
   canary[slot] = nonce;
@@ -302,7 +301,7 @@ hsv_verify_tx_fused_kernel(const uint8_t *__restrict__ txs, const uint64_t *__re
     }
     const uint32_t meta = rec[18ull * n + li];
     const bool own = valid && !(meta & kPrepFallback);
-    const uint32_t f = verify_one_prepped<WA, CB>(pkw, rw, rec + li, n, meta, comb_b, vt);
+    const uint32_t f = verify_one_prepped<WA, CB, joint_pointpass<WA>()>(pkw, rw, rec + li, n, meta, comb_b, vt);
     bad |= ((f & kFault) ? 1u : 0u) | (canary[slot] != nonce ? 2u : 0u);
     if (own && flags_out) flags_out[idx] = (uint8_t)f;
     if (strict_bits) {

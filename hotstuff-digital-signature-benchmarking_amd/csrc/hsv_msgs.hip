@@ -52,7 +52,7 @@ hsv_msg_prep_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const ui
     s[4] = s1.x; s[5] = s1.y; s[6] = s1.z; s[7] = s1.w;
   }
   if (i_in < n) {
-    const bool fallback = prep_from_hash<4, PutPlain, true>(hw, s, prep + i, n, lat_bits, !ok);
+    const bool fallback = prep_from_hash<4, PutPlain, true, pointpass_digit_bits<4>()>(hw, s, prep + i, n, lat_bits, !ok);
     if (fallback) fb_list[atomicAdd(fb_count, 1u)] = i;
   }
 }

@@ -5,7 +5,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "hsv_verify_core.hpp"
+#include "hsv_verify_hc.hpp"
 
 #ifndef HSV_HP_WAVES
 #define HSV_HP_WAVES 3  // waves per SIMD of the point pass (launch bounds: 168 VGPRs)
@@ -65,6 +68,59 @@ struct GlobalVarTab {
 
 template <int WA>
 constexpr int vt_lane_uint4() { return 2 * (1 << (WA - 1)) * 8; }
+
+// The joint table of the throughput point pass (hsv_verify_hc.hpp, jt_build /
+// straus_joint): kJointLines lines of 128 B per lane, line l at
+// base + (l - 1) * 8; line 0, the identity, is the shared one.  The
+// full-length path of a fallback item keeps its 8-line table of -A in the
+// same slot (put / get, table 0 of GlobalVarTab<9>: lines 1 .. 8).
+// Fault injection as GlobalVarTab: zeros in every line, or one bit flipped in
+// the lines that involve R (and in the fallback path's table 0).
+struct GlobalJointTab {
+  uint4 *base;
+  uint32_t inject = kInjectNone;
+  __device__ __forceinline__ void put(int t, int m, const uint32_t w[32]) const {
+    GlobalVarTab<9>{base, inject}.put(t, m, w);
+  }
+  __device__ __forceinline__ void get(int t, uint32_t m, uint32_t w[32]) const {
+    GlobalVarTab<9>{base, inject}.get(t, m, w);
+  }
+  __device__ __forceinline__ void put_line(uint32_t l, const uint32_t w[32]) const {
+    uint4 *e = base + (l - 1u) * 8u;
+    if (__builtin_expect(inject == kInjectZeroTables || (inject == kInjectFlipTables && l >= kJointFirstLineOfR), 0)) {
+      HSV_UNROLL
+      for (int q = 0; q < 8; ++q)
+        e[q] = inject == kInjectZeroTables ? make_uint4(0u, 0u, 0u, 0u)
+                                           : make_uint4(w[4 * q] ^ (q == 0 ? 1u : 0u), w[4 * q + 1], w[4 * q + 2],
+                                                        w[4 * q + 3]);
+      return;
+    }
+    HSV_UNROLL
+    for (int q = 0; q < 8; ++q) {
+#ifdef HSV_TIMING_STUB_TABLE_STORES  // timing probe only: lines computed, never stored
+      asm volatile("" ::"v"(w[4 * q]), "v"(w[4 * q + 1]), "v"(w[4 * q + 2]), "v"(w[4 * q + 3]));
+#else
+      e[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+#endif
+    }
+  }
+  __device__ __forceinline__ void get_line(uint32_t l, uint32_t w[32]) const {
+    const uint4 *e = l ? base + (l - 1u) * 8u : kVtIdentity;
+    HSV_UNROLL
+    for (int q = 0; q < 8; ++q) {
+      const uint4 v = e[q];
+      w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
+    }
+  }
+};
+constexpr int kJointLaneUint4 = kJointLines * 8;  // 96 uint4 = 1.5 KiB per lane
+static_assert(kJointLines >= 8, "the fallback path's 8-line table shares the slot");
+
+// the throughput point pass's table type and slot size (joint_pointpass, hsv_verify_hc.hpp)
+template <int WA>
+using PointPassTab = std::conditional_t<joint_pointpass<WA>(), GlobalJointTab, GlobalVarTab<(1 << (WA - 1)) + 1>>;
+template <int WA>
+constexpr int pointpass_lane_uint4() { return joint_pointpass<WA>() ? kJointLaneUint4 : vt_lane_uint4<WA>(); }
 
 
 // one (pk, sig, msg) record into words

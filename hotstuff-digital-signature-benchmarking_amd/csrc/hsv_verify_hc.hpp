@@ -14,6 +14,15 @@
 // window loop is ~3k instructions instead of ~10k and stays in the shared
 // instruction cache.  A lane whose lattice reduction fails (~2^-22.6) takes
 // verify_one_full_comb: the same two phases with the full-length k.
+//
+// The throughput point pass (hsv_verify_hp_kernel, the fused transaction
+// launch) runs phase 1 over ONE joint table instead (jt_build, straus_joint,
+// the JOINT form of verify_one_prepped): the 12 lines i(-R) + j(-A) of the
+// sign-folded pairs of signed radix-4 digits, 70 columns of 2 bits with two
+// doublings and one cached addition each -- the same doublings and additions
+// per bit, four table lines fewer to build, pack, store and read back.  Its
+// prepasses write the record's digits as 2-bit columns (prep_from_hash, DW = 2).
+// The latency forms and the committee kernels keep the two 4-bit tables.
 #pragma once
 #include "hsv_comb.hpp"
 #include "hsv_lattice.hpp"
@@ -251,19 +260,26 @@ struct PutPlain {
 // the message again, so a fallback item's eight b words -- meaningless for it
 // -- carry k mod l instead; and an item marked `skip` (its message range is
 // malformed) gets the meta word kPrepVoid alone: the point pass answers flags 0.
+// DW: the digit width of the record's ten digit words.  DW = WA is the format
+// of straus_vt (NW windows of WA bits); DW = 2 the joint point pass's: 70
+// columns of signed radix-4 digits chunk - 2 in {-2, -1, 0, 1}, top-aligned in
+// the same five words (straus_joint).  Nothing else in the record depends on it.
 constexpr uint32_t kPrepVoid = 8u;
-template <int WA, class Put = PutPlain, bool KREC = false>
+// c + C_2 < 2^140 needs c < 2^140 / 3: the 138-bit lattice bound leaves room
+static_assert(kLatCombBits + 2 <= HalfCombWindows<2>::BITS && HalfCombWindows<2>::NW == 70,
+              "2-bit columns: c < 2^138 plus the recoding constant (0.667 * 2^140) must stay below 2^140");
+template <int WA, class Put = PutPlain, bool KREC = false, int DW = WA>
 HSV_INL bool prep_from_hash(const uint32_t h[16], const uint32_t s[8], uint32_t *rec, uint64_t stride,
                             int lat_bits = kLatCombBits, bool skip = false) {
-  using G = HalfCombWindows<WA>;
+  using G = HalfCombWindows<DW>;
   const uint32_t s_ok = sc_is_canonical(s);
   const sc k = sc_reduce512(h);
   const LatOut lat = lattice_reduce(k, lat_bits);
   uint32_t d[5];
-  recode_top5<WA, G::NW>(lat.c1, d);
+  recode_top5<DW, G::NW>(lat.c1, d);
   HSV_UNROLL
   for (int i = 0; i < 5; ++i) Put::u32(rec + i * stride, d[i]);
-  recode_top5<WA, G::NW>(lat.c0, d);
+  recode_top5<DW, G::NW>(lat.c0, d);
   HSV_UNROLL
   for (int i = 0; i < 5; ++i) Put::u32(rec + (5 + i) * stride, d[i]);
   const sc b = sc_mul_small(lat.c1, s);
@@ -274,12 +290,12 @@ HSV_INL bool prep_from_hash(const uint32_t h[16], const uint32_t s[8], uint32_t 
   return !lat.ok && !(KREC && skip);
 }
 
-template <int WA, class Put = PutPlain>
+template <int WA, class Put = PutPlain, int DW = WA>
 HSV_INL bool prep_scalars(const uint32_t pk[8], const uint32_t sig[16], const uint32_t msg[8], uint32_t *rec,
                           uint64_t stride, int lat_bits = kLatCombBits) {
   uint32_t h[16];
   sha512_96(sig, pk, msg, h);
-  return prep_from_hash<WA, Put>(h, sig + 8, rec, stride, lat_bits);
+  return prep_from_hash<WA, Put, false, DW>(h, sig + 8, rec, stride, lat_bits);
 }
 
 // Point pass of a prepped item: the half-size equation of
@@ -299,11 +315,147 @@ HSV_INL bool prep_scalars(const uint32_t pk[8], const uint32_t sig[16], const ui
   } while (0)
 #endif
 
-template <int WA, int CB, class VT>
+// ---- joint table over 2-bit columns ------------------------------------------
+// With P = -R and Q = -A, a column of the two scalars' signed radix-4 digits
+// (i, j), j already flipped by the sign of c0, adds iP + jQ: one addition per
+// 2 bits from ONE table, where straus_vt spends two per 4 bits from two.  The
+// doublings and additions per bit are the same; the table is 12 lines instead
+// of 16 and costs 2 doublings + 8 additions to build instead of 2 + 12.
+// Folded by sign, i in {0, 1, 2} and j in {-2 .. 2} (i = 0: j >= 0): with
+// s = 5i + j the line is |s| and the fold is s < 0, since |j| <= 2 < 5 --
+//   0 the identity (the shared line), 1, 2 = Q, 2Q, 5i + j the lines with P
+//   (3 .. 7 = P - 2Q .. P + 2Q, 8 .. 12 = 2P - 2Q .. 2P + 2Q).
+//   VT::put_line(l, const uint32_t w[32])   store line l (1 .. kJointLines)
+//   VT::get_line(l, uint32_t w[32])         load it back (0: the identity)
+constexpr int kJointLines = 12;
+constexpr uint32_t kJointFirstLineOfR = 3;  // lines below hold multiples of Q alone
+
+HSV_INL uint32_t joint_line(int i, int j, uint32_t &neg) {
+  const int s = 5 * i + j;
+  neg = s < 0;
+  return (uint32_t)(s < 0 ? -s : s);
+}
+
+// a column's line and fold from the two scalars' 2-bit chunks (digit =
+// chunk - 2); flip: c0 < 0, the digit of |c0| changes sign
+HSV_INL uint32_t joint_column(uint32_t ci, uint32_t cj, uint32_t flip, uint32_t &neg) {
+  const int j = (int)cj - 2;
+  return joint_line((int)ci - 2, flip ? -j : j, neg);
+}
+
+template <class VT>
+HSV_INL void jt_put(VT &vt, uint32_t line, const ge_ext &p) {
+  uint32_t w[32];
+  cached_pack(ge_to_cached(p), w);
+  vt.put_line(line, w);
+}
+
+// Lines ls <- P + Q and ld <- P - Q for a cached Q.  The sum's and the
+// difference's cross products differ; C = T1 2dT2 and D = Z1 2Z2 are shared,
+// with F and G swapped for the difference.  Operand classes as
+// ge_add_cached_rt.  All six products come first and the sum is stored before
+// the difference is finished, so that neither Q nor the sum stays live.
+template <class VT>
+HSV_INL void jt_pair(VT &vt, const ge_ext &p, const ge_cached &q, uint32_t ls, uint32_t ld) {
+  const fe a = fe_sub(p.Y, p.X), b = fe_add(p.Y, p.X);
+  fe A, B, A2, B2, C, D;
+  fe_mul2(p.T, q.T2d, p.Z, q.Z2, C, D);
+  fe_mul2(a, q.YmX, b, q.YpX, A, B);
+  fe_mul2(a, q.YpX, b, q.YmX, A2, B2);
+  const fe F = fe_sub(D, C), G = fe_add(D, C);
+  jt_put(vt, ls, ge_finish_rt(fe_sub(B, A), F, G, fe_add(B, A), true));
+  jt_put(vt, ld, ge_finish_rt(fe_sub(B2, A2), G, F, fe_add(B2, A2), true));
+}
+
+// The 12 lines for the affine points P = (xp, yp), Q = (xq, yq).  Q and 2Q
+// first; then for P and 2P the line itself and its sums and differences with
+// Q and 2Q, which are read back from the table: one pair body in a loop.
+template <class VT>
+HSV_INL void jt_build(VT &vt, const fe &xp, const fe &yp, const fe &xq, const fe &yq) {
+#ifdef HSV_TIMING_STUB_TABLES  // tools/phase_probe.py only: tables left unwritten
+  return;
+#endif
+  ge_ext p, q;
+  p.X = xp;
+  p.Y = yp;
+  p.Z = fe_small(1);
+  q.X = xq;
+  q.Y = yq;
+  q.Z = fe_small(1);
+  fe_mul2(xp, yp, xq, yq, p.T, q.T);
+  uint32_t neg;
+  jt_put(vt, joint_line(0, 1, neg), q);
+  jt_put(vt, joint_line(0, 2, neg), ge_dbl_rt(q, true));
+  HSV_NOUNROLL
+  for (int i = 1; i <= 2; ++i) {
+    if (i == 2) p = ge_dbl_rt(p, true);
+    jt_put(vt, joint_line(i, 0, neg), p);
+    HSV_NOUNROLL
+    for (int j = 1; j <= 2; ++j) {
+      uint32_t w[32];
+      vt.get_line(joint_line(0, j, neg), w);
+      jt_pair(vt, p, cached_unpack(w), joint_line(i, j, neg), joint_line(i, -j, neg));
+    }
+  }
+}
+
+// Straus over the joint table: d[0] the digits of c1, d[1] those of |c0| (five
+// words each, NW 2-bit columns, the top column at the top bit); flip: c0 < 0.
+// Per column two doublings and one cached addition of +-line; T only where
+// the addition follows, and after the last column (the comb phase follows).
+// Leading columns that are zero in every lane of the wave are skipped, as in
+// straus_vt.  The line is loaded right before its addition.
+template <int NW, class VT>
+HSV_INL ge_ext straus_joint(uint32_t d[2][5], VT &vt, uint32_t flip) {
+  ge_ext q = ge_identity();
+#ifdef HSV_TIMING_STUB_STRAUS  // tools/phase_probe.py only
+  return q;
+#endif
+  int top = NW - 1;
+  HSV_NOUNROLL
+  while (top > 0) {
+    const uint32_t nz = ((d[0][4] >> 30) ^ 2u) | ((d[1][4] >> 30) ^ 2u);
+    if (wave_any(nz)) break;
+    limbs_shl<5>(d[0], 2);
+    limbs_shl<5>(d[1], 2);
+    --top;
+  }
+  HSV_NOUNROLL
+  for (int c = top; c >= 0; --c) {
+    uint32_t neg;
+    const uint32_t line = joint_column(d[0][4] >> 30, d[1][4] >> 30, flip, neg);
+    limbs_shl<5>(d[0], 2);
+    limbs_shl<5>(d[1], 2);
+    if (c != top) {
+      HSV_NOUNROLL
+      for (int j = 0; j < 2; ++j) q = ge_dbl_rt(q, j == 1);
+    }
+    uint32_t cur[32];
+    vt.get_line(line, cur);
+    q = ge_add_cached_rt(q, ge_cached_cneg(cached_unpack(cur), neg), c == 0);
+  }
+  return q;
+}
+
+// Which point pass hsv_verify_hp_kernel and the fused transaction launch run,
+// and so which digit format their prepasses write (hsv_prep_kernel, the
+// transaction record kernels, hsv_msg_prep_kernel): the joint table over
+// 2-bit columns, or (0, A/B builds only) the two 4-bit tables.
+#ifndef HSV_JOINT_POINTPASS
+#define HSV_JOINT_POINTPASS 1
+#endif
+template <int WA>
+constexpr bool joint_pointpass() { return HSV_JOINT_POINTPASS && WA == 4; }
+template <int WA>
+constexpr int pointpass_digit_bits() { return joint_pointpass<WA>() ? 2 : WA; }
+
+// JOINT: the record holds 2-bit columns (prep_from_hash with DW = 2) and the
+// point pass runs over the joint table; otherwise two WA-bit tables.
+template <int WA, int CB, bool JOINT = false, class VT>
 HSV_INL uint32_t verify_one_prepped(const uint32_t pk[8], const uint32_t rb[8], const uint32_t *rec,
                                     uint64_t stride, const uint32_t meta, const uint32_t *tb, VT &vt,
                                     uint64_t *clk = nullptr) {
-  using G = HalfCombWindows<WA>;
+  using G = HalfCombWindows<JOINT ? 2 : WA>;
   constexpr int TS = 1 << (WA - 1);
   uint32_t a_ok, small_a, r_ok, small_r;
   {
@@ -312,8 +464,12 @@ HSV_INL uint32_t verify_one_prepped(const uint32_t pk[8], const uint32_t rb[8], 
     small_r = r_ok & y_is_small_order(yr);
     small_a = a_ok & y_is_small_order(ya);
     HSV_CLK(1);
-    vt_build<TS>(vt, 0, fe_carry(fe_neg(xr)), yr);
-    vt_build<TS>(vt, 1, fe_carry(fe_neg(xa)), ya);
+    if constexpr (JOINT) {
+      jt_build(vt, fe_carry(fe_neg(xr)), yr, fe_carry(fe_neg(xa)), ya);
+    } else {
+      vt_build<TS>(vt, 0, fe_carry(fe_neg(xr)), yr);
+      vt_build<TS>(vt, 1, fe_carry(fe_neg(xa)), ya);
+    }
     HSV_CLK(2);
   }
   uint32_t d[2][5];
@@ -322,7 +478,10 @@ HSV_INL uint32_t verify_one_prepped(const uint32_t pk[8], const uint32_t rb[8], 
     d[0][i] = rec[i * stride];
     d[1][i] = rec[(5 + i) * stride];
   }
-  ge_ext q = straus_vt<WA, G::NW, 5, 2, false>(d, vt, (meta & kPrepC0Neg) ? 1u : 0u);
+  const uint32_t c0_neg = (meta & kPrepC0Neg) ? 1u : 0u;
+  ge_ext q;
+  if constexpr (JOINT) q = straus_joint<G::NW>(d, vt, c0_neg);
+  else q = straus_vt<WA, G::NW, 5, 2, false>(d, vt, c0_neg);
   HSV_CLK(3);
   uint32_t b[8];
   HSV_UNROLL
