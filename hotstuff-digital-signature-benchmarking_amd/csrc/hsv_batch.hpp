@@ -4,8 +4,8 @@
 // A batch is ragged -- item i is bytes [offsets[i], offsets[i + 1]) of the
 // caller's buffer, n + 1 non-decreasing offsets -- or fixed: item i is `len`
 // bytes at i * stride (stride 0: every item is the same `len` bytes).
-// hsv_verify_transactions*, hsv_verify_msgs and hsv_signer_sign_transactions
-// stage such a batch chunk by chunk: at most max_items items and max_bytes
+// hsv_verify_transactions*, hsv_verify_msgs, hsv_signer_sign_transactions and
+// hsv_signer_sign_msgs stage such a batch chunk by chunk: at most max_items items and max_bytes
 // bytes per launch, an item larger than max_bytes alone in its chunk.
 #pragma once
 #include <algorithm>

@@ -319,6 +319,19 @@ size_t hsvi_set_tx_sign_chunk(size_t items);
 // Items per lane (G) of the following signer launches: one of the built
 // values (1, 2, 4, 8, 16), 0 = the product's; previous value or -1.
 int hsvi_set_signer_group(int g);
+int hsvi_signer_group(void);  // the G in force
+// Whole messages of any lengths signed into 64-byte slots (hsv_msgsign.hpp):
+// message i = msgs[offsets[i], offsets[i+1]) or msg_len bytes at msgs + i *
+// msg_stride, any alignment; R || s to sig + i * sig_stride (multiples of 16).
+// Three launches on `stream` (hsv_msgsign.hip): nonce, point, response.  A key
+// index out of range or a decreasing pair of offsets gives 64 zero bytes.
+hipError_t hsv_launch_msg_sign(const uint8_t *keys, uint32_t nkeys, const uint32_t *key_idx, const uint8_t *msgs,
+                               const uint64_t *offsets, uint64_t msg_len, uint64_t msg_stride, uint32_t m,
+                               uint8_t *sig, uint64_t sig_stride, const uint32_t *comb16, uint32_t *fault,
+                               hipStream_t stream);
+// Items per round of hsv_signer_sign_msgs* (tests; 0 = the default 2^22);
+// previous value.
+size_t hsvi_set_msg_sign_chunk(size_t items);
 #ifdef __cplusplus
 }
 #endif

@@ -104,4 +104,58 @@ __device__ __forceinline__ bool msg_hash_lane(const uint8_t *__restrict__ pk, ui
   return ok;
 }
 
+// hw = SHA-512(head || M) with the HB / 4 head words from the caller (the
+// signer's launches, hsv_msgsign.hip: the prefix, or R || pk gathered through
+// key_idx, which a pointer and a stride do not describe); M = mlen bytes at
+// msgs + lo.  HB = 32: the window of block 0 is 96 bytes at any offset, 7
+// chunks; HB = 64: 64 bytes, 5 chunks; later windows 9, as above.  The
+// conventions are msg_hash_lane's: every lane of the wave calls this, the trip
+// count is the wave's longest message, nothing is stored to global memory, a
+// window without a message byte and an empty message load nothing.
+template <int HB>
+__device__ __forceinline__ void msg_hash_wave(const uint32_t head[HB / 4], const uint8_t *__restrict__ msgs,
+                                              uint64_t lo, uint64_t mlen, uint32_t lane, uint4 *stage,
+                                              uint32_t hw[16]) {
+  constexpr int NW0 = (128 - HB) / 4;  // message words of block 0
+  constexpr int Q0 = NW0 / 4 + 1;
+  static_assert(Q0 <= kMsgQ, "block 0 stages through the same LDS");
+  const uintptr_t base = reinterpret_cast<uintptr_t>(msgs);
+  const uint4 *q = reinterpret_cast<const uint4 *>(base & ~uintptr_t(15));
+  const uint64_t start = (uint64_t)(base & 15u) + lo;
+  const uint64_t q_last = mlen ? (start + mlen - 1) >> 4 : kNoChunk;  // an empty message loads nothing
+
+  uint64_t h[8];
+  sha512_init(h);
+  const uint64_t nblocks = head_num_blocks<HB>(mlen);
+  uint32_t wave_blocks = (uint32_t)nblocks;
+  HSV_UNROLL
+  for (int m = 1; m < 64; m <<= 1) wave_blocks = max(wave_blocks, (uint32_t)__shfl_xor((int)wave_blocks, m, 64));
+  const uint32_t sh16 = (uint32_t)(start & 15u);
+  const bool wave_aligned = __all(sh16 == 0u || mlen == 0);
+  HSV_NOUNROLL
+  for (uint32_t b = 0; b < wave_blocks; ++b) {
+    uint64_t w[16];
+    const uint64_t off = head_block_offset<HB>(b);
+    const uint64_t last = off < mlen ? q_last : kNoChunk;  // a window without a message byte is not loaded
+    if (b == 0) {
+      uint32_t raw[4 * Q0 + 1], words[NW0];
+      tx_stage_chunks<Q0>(q, stage, lane, start >> 4, last, raw);
+      msg_words<NW0>(raw, wave_aligned, sh16, words);
+      head_block0_words<HB>(head, words, mlen, w);
+    } else {
+      uint32_t raw[4 * kMsgQ + 1], words[32];
+      tx_stage_chunks<kMsgQ>(q, stage, lane, (start + off) >> 4, last, raw);
+      msg_words<32>(raw, wave_aligned, sh16, words);
+      const bool wave_full = __all(off + 128u <= mlen);
+      if (wave_full) msg_block_words_full(words, w);
+      else head_block_words<HB>(words, mlen, b, w);
+    }
+    if (b < nblocks) {
+      if (b + 1 == nblocks) head_length_field<HB>(w, mlen);
+      sha512_compress(h, w);
+    }
+  }
+  msg_digest_words(h, hw);
+}
+
 }  // namespace hsv

@@ -317,6 +317,7 @@ struct SignArgs {
 // live, and R || s goes to the item's aligned 64-byte slot.  The transaction
 // signer's is TxSignIo (hsv_txsign.hpp).
 struct SignSlotIo {
+  static constexpr bool kPointOnly = false;  // sign_lane hashes: true only for MsgSignIo (hsv_msgsign.hpp)
   // kSlotOk (sign), kSlotZero (zero output) or kSlotDead (the item is skipped: nothing is written)
   HSV_MEMBER uint32_t slot(const SignArgs &a, uint64_t, uint32_t ki) const { return ki < a.nkeys ? kSlotOk : kSlotZero; }
   // status: kSlotOk (sigw = R || s), kSlotZero or kSlotFault (sigw = 0)
@@ -326,6 +327,9 @@ struct SignSlotIo {
 };
 
 // FAST: msg_len == 32 (the Digest): both hashes are one block each.
+// Io::kPointOnly (the point launch of hsv_signer_sign_msgs*, hsv_msgsign.hpp):
+// neither hash is taken here -- r comes from io.nonce_words(), and store()
+// receives enc(R) in sigw[0..8) and nothing else.
 template <int WB, int G, bool FAST, class Store, class Io = SignSlotIo>
 HSV_INL uint32_t sign_lane(const SignArgs &a, uint64_t first, uint32_t step, Store &st, const Io &io = Io()) {
   fe pp = fe_small(1);
@@ -338,20 +342,27 @@ HSV_INL uint32_t sign_lane(const SignArgs &a, uint64_t first, uint32_t step, Sto
       const uint32_t ki = a.key_idx ? a.key_idx[i] : (uint32_t)i;
       status = io.slot(a, i, ki);
       if (status == kSlotOk) {
-        const uint8_t *mp = a.msg + i * a.msg_stride;
-        uint32_t in[16], h[16];
-        sign_load16<8>(a.keys + (uint64_t)ki * kSignKeyBytes + 32, in);  // prefix
-        if (FAST) {
-          sign_load_msg32(mp, in + 8);
-          sha512_words<16>(in, h);
+        sc r;
+        if constexpr (Io::kPointOnly) {
+          io.nonce_words(i, r.v);
         } else {
-          sha512_head_msg<8>(in, mp, a.msg_len, h);
+          const uint8_t *mp = a.msg + i * a.msg_stride;
+          uint32_t in[16], h[16];
+          sign_load16<8>(a.keys + (uint64_t)ki * kSignKeyBytes + 32, in);  // prefix
+          if (FAST) {
+            sign_load_msg32(mp, in + 8);
+            sha512_words<16>(in, h);
+          } else {
+            sha512_head_msg<8>(in, mp, a.msg_len, h);
+          }
+          r = sc_reduce512(h);
         }
-        const sc r = sc_reduce512(h);
         const uint32_t inj = (a.inject != kInjectNone && i == a.inject_item) ? a.inject : (uint32_t)kInjectNone;
         const uint32_t ok = group_push(fixed_base_comb<WB>(r.v, a.table, inj), pp, st, g);
-        HSV_UNROLL
-        for (int j = 0; j < 8; ++j) st.put(g, kWsR + j, r.v[j]);
+        if constexpr (!Io::kPointOnly) {
+          HSV_UNROLL
+          for (int j = 0; j < 8; ++j) st.put(g, kWsR + j, r.v[j]);
+        }
         status = ok ? kSlotOk : kSlotFault;
         bad |= ok ^ 1u;
       }
@@ -370,7 +381,12 @@ HSV_INL uint32_t sign_lane(const SignArgs &a, uint64_t first, uint32_t step, Sto
     if (status != kSlotZero) {
       uint32_t enc[8];
       group_pop(inv, st, g, enc);
-      if (status == kSlotOk) {
+      if constexpr (Io::kPointOnly) {
+        if (status == kSlotOk) {
+          HSV_UNROLL
+          for (int j = 0; j < 8; ++j) sigw[j] = enc[j];
+        }
+      } else if (status == kSlotOk) {
         const uint32_t ki = a.key_idx ? a.key_idx[i] : (uint32_t)i;
         const uint8_t *key = a.keys + (uint64_t)ki * kSignKeyBytes;
         const uint8_t *mp = a.msg + i * a.msg_stride;

@@ -18,23 +18,12 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
-#include <type_traits>
 
 #include "hsv_internal.h"
-#include "hsv_sign_core.hpp"
+#include "hsv_sign_launch.hpp"
 #include "hsv_txsign.hpp"
 
 namespace hsv {
-
-constexpr int kSignBlock = 256;
-
-// Slot g, word w of this lane: base[(g * kSignWsWords + w) * 64] -- one word of
-// all 64 lanes is one 256-byte line.
-struct LaneStore {
-  uint32_t *base;
-  __device__ __forceinline__ void put(int g, int w, uint32_t v) { base[(uint32_t)(g * kSignWsWords + w) * 64u] = v; }
-  __device__ __forceinline__ uint32_t get(int g, int w) const { return base[(uint32_t)(g * kSignWsWords + w) * 64u]; }
-};
 
 template <int G>
 __global__ void __launch_bounds__(kSignBlock) hsv_keygen_kernel(KeygenArgs a, uint32_t *__restrict__ ws,
@@ -78,33 +67,13 @@ namespace {
 constexpr int kGroups[] = {1, 2, 4, 8, 16};
 std::atomic<int> g_group{hsv::kSignGroup};
 
-struct Grid {
-  uint32_t blocks;
-  size_t ws_bytes;
-};
-Grid grid_for(uint64_t n, int group) {
-  const uint64_t per_block = (uint64_t)hsv::kSignBlock * group;
-  const uint64_t blocks = (n + per_block - 1) / per_block;
-  return {(uint32_t)blocks, (size_t)(blocks * per_block * hsv::kSignWsWords * sizeof(uint32_t))};
-}
-
-// fn(std::integral_constant<int, G>) for the built G that `group` names
-template <class Fn>
-void with_group(int group, Fn &&fn) {
-  switch (group) {
-    case 1: fn(std::integral_constant<int, 1>{}); break;
-    case 2: fn(std::integral_constant<int, 2>{}); break;
-    case 4: fn(std::integral_constant<int, 4>{}); break;
-    case 8: fn(std::integral_constant<int, 8>{}); break;
-    default: fn(std::integral_constant<int, 16>{}); break;
-  }
-}
-
 }  // namespace
 
 // G of the following launches (measurement hook, csrc/hsv_test_hooks.h):
 // 0 restores the product's; returns the previous value, or -1 for a value
 // that is not built.
+extern "C" int hsvi_signer_group(void) { return g_group.load(); }
+
 extern "C" int hsvi_set_signer_group(int g) {
   if (g == 0) g = hsv::kSignGroup;
   for (int b : kGroups)
@@ -117,12 +86,12 @@ extern "C" hipError_t hsv_launch_keygen(const uint8_t *seeds, uint32_t n, uint8_
   if (n == 0) return hipSuccess;
   if (n > (1u << 22)) return hipErrorInvalidValue;
   const int group = g_group.load();
-  const Grid gr = grid_for(n, group);
+  const hsv::SignGrid gr = hsv::sign_grid_for(n, group);
   hsv::Workspace ws(nullptr, 0, gr.ws_bytes, stream);
   if (ws.status() != hipSuccess) return ws.status();
   const hsv::KeygenArgs a{seeds, n, keys, comb16, hsv::kInjectNone, 0u};
   uint32_t *w = reinterpret_cast<uint32_t *>(ws.get());
-  with_group(group, [&](auto g) {
+  hsv::sign_with_group(group, [&](auto g) {
     hipLaunchKernelGGL((hsv::hsv_keygen_kernel<decltype(g)::value>), dim3(gr.blocks), dim3(hsv::kSignBlock), 0, stream,
                        a, w, fault);
   });
@@ -136,12 +105,12 @@ extern "C" hipError_t hsv_launch_sign(const uint8_t *keys, uint32_t nkeys, const
   if (m == 0) return hipSuccess;
   if (m > (1u << 22)) return hipErrorInvalidValue;
   const int group = g_group.load();
-  const Grid gr = grid_for(m, group);
+  const hsv::SignGrid gr = hsv::sign_grid_for(m, group);
   hsv::Workspace ws(nullptr, 0, gr.ws_bytes, stream);
   if (ws.status() != hipSuccess) return ws.status();
   const hsv::SignArgs a{keys, nkeys, key_idx, msg, msg_len, msg_stride, m, sig, sig_stride, comb16, hsv::kInjectNone, 0u};
   uint32_t *w = reinterpret_cast<uint32_t *>(ws.get());
-  with_group(group, [&](auto g) {
+  hsv::sign_with_group(group, [&](auto g) {
     constexpr int G = decltype(g)::value;
     if (a.msg_len == 32)
       hipLaunchKernelGGL((hsv::hsv_sign_kernel<G, true>), dim3(gr.blocks), dim3(hsv::kSignBlock), 0, stream, a, w, fault);
@@ -159,7 +128,7 @@ extern "C" hipError_t hsv_launch_tx_sign(const uint8_t *keys, uint32_t nkeys, co
   if (m == 0) return hipSuccess;
   if (m > (1u << 22)) return hipErrorInvalidValue;
   const int group = g_group.load();
-  const Grid gr = grid_for(m, group);
+  const hsv::SignGrid gr = hsv::sign_grid_for(m, group);
   // the signing workspace | m digests of 32 B | m status words
   const size_t off_dig = gr.ws_bytes, off_status = off_dig + (size_t)m * 32;
   hsv::Workspace ws(nullptr, 0, off_status + (size_t)m * 4, stream);
@@ -171,7 +140,7 @@ extern "C" hipError_t hsv_launch_tx_sign(const uint8_t *keys, uint32_t nkeys, co
     const hsv::SignArgs a{keys, nkeys, key_idx, d + off_dig, 32, 32, m, nullptr, 0, comb16, hsv::kInjectNone, 0u};
     const hsv::TxSignIo io{status, txs, offsets, tx_size};
     uint32_t *w = reinterpret_cast<uint32_t *>(d);
-    with_group(group, [&](auto g) {
+    hsv::sign_with_group(group, [&](auto g) {
       hipLaunchKernelGGL((hsv::hsv_tx_sign_kernel<decltype(g)::value>), dim3(gr.blocks), dim3(hsv::kSignBlock), 0,
                          stream, a, io, w, fault);
     });

@@ -8,6 +8,9 @@
 // hsv_signer_sign_transactions* is the signing mirror of hsv_verify_transactions*
 // (the client's half of mempool/src/batch_maker.rs:79-85): pk || R || s into the
 // last 96 bytes of every transaction, in place (csrc/hsv_txsign.hpp).
+// hsv_signer_sign_msgs* is the signing mirror of hsv_verify_msgs*: whole
+// messages of any lengths, by offsets or at a fixed stride, in three launches
+// per round (csrc/hsv_msgsign.hpp).
 #include <algorithm>
 #include <memory>
 #include <string>
@@ -70,10 +73,28 @@ hipError_t tx_sign_chunks(const hsv_signer &s, const uint32_t *d_key_idx, uint8_
   return e;
 }
 
+// ---- whole messages (hsv_signer_sign_msgs*) --------------------------------------
+std::atomic<size_t> g_msg_chunk{kChunk};  // items per round (hsvi_set_msg_sign_chunk: tests)
+
+// One round: items [base, base + k) of a batch whose keys, when key_idx is
+// NULL, are those of items first.. (item i uses key i).
+hipError_t msg_sign_round(const hsv_signer &s, size_t first, const uint32_t *d_key_idx, const uint8_t *d_msgs,
+                          const uint64_t *d_offsets, size_t msg_len, size_t msg_stride, size_t k, uint8_t *d_sig,
+                          size_t sig_stride, const uint32_t *comb16, uint32_t *fault, hipStream_t stream) {
+  const size_t kb = std::min(first, s.n);
+  return hsv_launch_msg_sign(s.d_keys + (d_key_idx ? 0 : kb * 96), (uint32_t)(d_key_idx ? s.n : s.n - kb), d_key_idx,
+                             d_msgs, d_offsets, msg_len, msg_stride, (uint32_t)k, d_sig, sig_stride, comb16, fault,
+                             stream);
+}
+
 }  // namespace
 
 extern "C" size_t hsvi_set_tx_sign_chunk(size_t items) {
   return g_tx_chunk.exchange(items == 0 || items > kChunk ? kChunk : items);
+}
+
+extern "C" size_t hsvi_set_msg_sign_chunk(size_t items) {
+  return g_msg_chunk.exchange(items == 0 || items > kChunk ? kChunk : items);
 }
 
 extern "C" {
@@ -269,6 +290,82 @@ int hsv_signer_sign_transactions(hsv_signer *s, const uint32_t *key_idx, uint8_t
     rc = blk.finish("hsv_signer_sign_transactions");
     if (offsets && copied && (rc == HSV_OK || rc == HSV_ERR_DEVICE_FAULT))
       for (size_t k = 0; k < m; ++k) std::memcpy(txs + first + rel[k + 1] - 96, back.data() + rel[k + 1] - 96, 96);
+    if (rc != HSV_OK) return rc;
+  }
+  return HSV_OK;
+}
+
+int hsv_signer_sign_msgs_device(const hsv_signer *s, const uint32_t *d_key_idx, const uint8_t *d_msgs,
+                                const uint64_t *d_offsets, size_t msg_len, size_t msg_stride, size_t m,
+                                uint8_t *d_sig, size_t sig_stride, uint32_t *d_fault, void *stream) {
+  if (m == 0) return HSV_OK;
+  // misaligned pointers are rejected before anything is looked at (as hsv_signer_sign_device)
+  if (((reinterpret_cast<uintptr_t>(d_sig) | sig_stride) & 15u) != 0)
+    return fail(HSV_ERR_ALIGN, "d_sig and sig_stride must be multiples of 16");
+  if (reinterpret_cast<uintptr_t>(d_key_idx) & 3u) return fail(HSV_ERR_ALIGN, "d_key_idx must be 4-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_offsets) & 7u) return fail(HSV_ERR_ALIGN, "d_offsets must be 8-byte aligned");
+  if (!s || !d_sig || (!d_msgs && !d_offsets && msg_len)) return fail(HSV_ERR_INVALID_ARG, "null argument");
+  if (!d_offsets && msg_stride != 0 && msg_stride < msg_len) return fail(HSV_ERR_INVALID_ARG, "messages overlap");
+  if (sig_stride < 64) return fail(HSV_ERR_INVALID_ARG, "signatures overlap");
+  if (m > 0xffffffffu) return fail(HSV_ERR_INVALID_ARG, "batch too large");
+  DeviceCall call;
+  const int rc = call.begin(d_sig, stream, d_fault, DeviceCall::kWide, "signer", s->device);
+  if (rc != HSV_OK) return rc;
+  if (!d_key_idx && m > s->n) return fail(HSV_ERR_INVALID_ARG, "more items than keys and no key_idx");
+  const size_t per = g_msg_chunk.load();
+  hipError_t e = hipSuccess;
+  // d_offsets are relative to d_msgs, so a round only moves along the offsets
+  for (size_t base = 0; base < m && e == hipSuccess; base += per)
+    e = msg_sign_round(*s, base, d_key_idx ? d_key_idx + base : nullptr,
+                       d_offsets ? d_msgs : d_msgs + base * msg_stride, d_offsets ? d_offsets + base : nullptr, msg_len,
+                       msg_stride, std::min(per, m - base), d_sig + base * sig_stride, sig_stride, call.comb,
+                       call.fault, call.stream);
+  return e == hipSuccess ? HSV_OK : hip_fail("message sign launch", e);
+}
+
+int hsv_signer_sign_msgs(hsv_signer *s, const uint32_t *key_idx, const uint8_t *msgs, const uint64_t *offsets,
+                         size_t msg_len, size_t msg_stride, size_t m, uint8_t *sig_out) {
+  if (m == 0) return HSV_OK;
+  if (!s || !sig_out) return fail(HSV_ERR_INVALID_ARG, "null argument");
+  int rc = msgs_host_args_ok(msgs, offsets, msg_len, msg_stride, m);  // the checks of hsv_verify_msgs
+  if (rc != HSV_OK) return rc;
+  rc = ensure_init();
+  if (rc != HSV_OK) return rc;
+  if (!key_idx && m > s->n) return fail(HSV_ERR_INVALID_ARG, "more items than keys and no key_idx");
+  DevCtx &c = ctx(s->device);
+  DeviceGuard guard(c.device);
+  if (guard.status() != hipSuccess) return hip_fail("hipSetDevice", guard.status());
+  rc = ensure_btable16(c);
+  if (rc != HSV_OK) return rc;
+  SlotLease lease(c);
+  Slot &slot = lease.slot();
+  rc = slot_prepare(slot, 0, 0);
+  if (rc != HSV_OK) return rc;
+  hipStream_t st = slot.stream;
+  const BatchSpan span{offsets, msg_stride, msg_len};
+  std::vector<uint64_t> rel;  // a round's offsets, relative to its first byte
+  for (size_t a = 0, b; a < m; a = b) {
+    b = span.chunk_end(a, m, g_msg_chunk.load(), g_stage_bytes.load());  // one round
+    const size_t k = b - a, bytes = span.span_bytes(a, b);
+    StagedBlock blk(st);
+    const size_t off_sig = blk.add(k * 64), off_idx = blk.add(key_idx ? k * 4 : 0);
+    const size_t off_offs = blk.add(offsets ? (k + 1) * 8 : 0), off_msg = blk.add(bytes);
+    rc = blk.alloc("allocating the message signing buffers");
+    if (rc != HSV_OK) return rc;
+    uint32_t *d_idx = key_idx ? reinterpret_cast<uint32_t *>(blk.at(off_idx)) : nullptr;
+    uint64_t *d_offs = offsets ? reinterpret_cast<uint64_t *>(blk.at(off_offs)) : nullptr;
+    if (key_idx) blk.in(off_idx, key_idx + a, k * 4);
+    if (offsets) {
+      rel.resize(k + 1);
+      span.rel_offsets(a, b, rel.data());
+      blk.in(off_offs, rel.data(), (k + 1) * 8);
+    }
+    if (msgs) blk.in(off_msg, msgs + span.first_byte(a), bytes);  // NULL: every message is empty
+    if (blk.ok())
+      blk.step(msg_sign_round(*s, a, d_idx, blk.at(off_msg), d_offs, msg_len, msg_stride, k, blk.at(off_sig), 64,
+                              c.d_btable16, blk.fault(), st));
+    blk.out(sig_out + a * 64, off_sig, k * 64);
+    rc = blk.finish("hsv_signer_sign_msgs");
     if (rc != HSV_OK) return rc;
   }
   return HSV_OK;

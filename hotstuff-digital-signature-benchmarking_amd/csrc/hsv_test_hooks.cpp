@@ -77,6 +77,7 @@ int hsv_test_tx_records(const uint8_t *d_txs, const uint64_t *d_offsets, size_t 
 }
 int hsv_test_signer_group(int g) { return hsvi_set_signer_group(g); }
 size_t hsv_test_tx_sign_chunk(size_t items) { return hsvi_set_tx_sign_chunk(items); }
+size_t hsv_test_msg_sign_chunk(size_t items) { return hsvi_set_msg_sign_chunk(items); }
 int hsv_test_committee_tx_counts(uint64_t out[3]) { return hsvh::committee_tx_counts(out); }
 int hsv_test_committee_msgs_counts(uint64_t out[3]) { return hsvh::committee_msgs_counts(out); }
 int hsv_test_msgs_small(int mode) { return hsvi_set_msgs_small(mode); }

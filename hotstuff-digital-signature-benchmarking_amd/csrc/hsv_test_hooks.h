@@ -84,8 +84,12 @@ HSV_API int hsv_test_signer_group(int g);
  * 2^22), so that a batch of a few hundred transactions crosses a launch
  * boundary.  0 restores the product's.  Returns the previous value. */
 HSV_API size_t hsv_test_tx_sign_chunk(size_t items);
+/* Tests: items per round of hsv_signer_sign_msgs* (the product's is 2^22), so
+ * that a batch of a few hundred messages crosses a round boundary.  0 restores
+ * the product's.  Returns the previous value. */
+HSV_API size_t hsv_test_msg_sign_chunk(size_t items);
 /* Tests: bytes of transactions or messages the host forms hsv_verify_transactions*,
- * hsv_verify_msgs and hsv_signer_sign_transactions stage per launch (the
+ * hsv_verify_msgs, hsv_signer_sign_transactions and hsv_signer_sign_msgs stage per launch (the
  * product's is 2^29; one larger item goes alone), so that a small batch takes
  * several launches and its offsets are rebased.  0 restores the product's.
  * Returns the previous value. */

@@ -100,6 +100,7 @@ HSV_INL void tx_store_tail(uint8_t *p, const uint32_t w[24]) {
 
 // ---- sign_lane's status and store for transactions ------------------------------
 struct TxSignIo {
+  static constexpr bool kPointOnly = false;
   const uint32_t *status;   // per item, from the digest launch
   uint8_t *txs;
   const uint64_t *offsets;  // or NULL: fixed tx_size

@@ -29,7 +29,7 @@ HOOKS = ("hsv_test_inject_fault", "hsv_test_inject_mode", "hsv_test_corrupt_auto
          "hsv_variant_available", "hsv_num_variants", "hsv_set_virtual_shards", "hsv_test_pipe_nocopy",
          "hsv_test_resident_counts", "hsv_test_resident_post_bad", "hsv_test_tx_records",
          "hsv_test_pipe_schedule", "hsv_test_numa_plan", "hsv_test_pinned_thread_cpus", "hsv_test_signer_group",
-         "hsv_test_tx_sign_chunk", "hsv_test_stage_bytes", "hsv_test_committee_tx_counts",
+         "hsv_test_tx_sign_chunk", "hsv_test_msg_sign_chunk", "hsv_test_stage_bytes", "hsv_test_committee_tx_counts",
          "hsv_test_committee_msgs_counts", "hsv_test_msgs_small", "hsv_test_msgs_form_counts")
 
 # flag bits (include/hsv.h)
@@ -156,7 +156,11 @@ def _declare(lib):
         "hsv_signer_sign_transactions_device": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u8p, c_u8p, sz, sz,
                                                                ctypes.c_void_p, ctypes.c_void_p]),
         "hsv_test_signer_group": (ctypes.c_int, [ctypes.c_int]),
+        "hsv_signer_sign_msgs": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u8p, c_u8p, sz, sz, sz, c_u8p]),
+        "hsv_signer_sign_msgs_device": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u8p, c_u8p, sz, sz, sz, c_u8p, sz,
+                                                       ctypes.c_void_p, ctypes.c_void_p]),
         "hsv_test_tx_sign_chunk": (sz, [sz]),
+        "hsv_test_msg_sign_chunk": (sz, [sz]),
         "hsv_test_stage_bytes": (sz, [sz]),
         "hsv_test_msgs_small": (ctypes.c_int, [ctypes.c_int]),
         "hsv_test_msgs_form_counts": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64)]),
@@ -167,6 +171,7 @@ def _declare(lib):
                              "hsv_signer_destroy", "hsv_signer_size", "hsv_signer_public_keys", "hsv_signer_sign",
                              "hsv_signer_sign_device", "hsv_verify_msgs", "hsv_verify_msgs_device",
                              "hsv_signer_sign_transactions", "hsv_signer_sign_transactions_device",
+                             "hsv_signer_sign_msgs", "hsv_signer_sign_msgs_device",
                              "hsv_committee_verify_transactions", "hsv_committee_verify_transactions_device",
                              "hsv_committee_verify_msgs", "hsv_committee_verify_msgs_device"}
     for name, (res, args) in sig.items():

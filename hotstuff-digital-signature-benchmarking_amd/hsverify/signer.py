@@ -6,7 +6,9 @@ The GPU form of the reference's ``generate_keypair`` and ``Signature::new``
 ``sign`` / ``sign_device`` produce RFC 8032 signatures bit-exact with
 ``verifier.sign_many``; ``sign_transactions`` / ``sign_transactions_device``
 fill in ``pk || R || s`` at the end of mempool transactions, the signing mirror
-of ``mempool.verify_transactions*``.  Not constant time (table lookups are indexed by
+of ``mempool.verify_transactions*``; ``sign_msgs`` / ``sign_msgs_device`` sign
+whole messages of differing lengths, the mirror of ``verifier.verify_msgs*``.
+Not constant time (table lookups are indexed by
 secret digits): never use it to hold a validator's key.  There is no CPU
 fallback; without a GPU the constructor raises.
 """
@@ -90,6 +92,58 @@ class Signer:
                 ctypes.c_void_p(msg.data_ptr()), length, stride, m, ctypes.c_void_p(sig.data_ptr()), sig.stride(0),
                 _fault_ptr(fault), ctypes.c_void_p(stream))
         _lib.check(rc, "hsv_signer_sign_device")
+
+    def sign_msgs(self, msgs, key_idx=None) -> np.ndarray:
+        """Whole messages of any lengths (hsv_signer_sign_msgs), the signing
+        mirror of ``verifier.verify_msgs``.  msgs: a sequence of m ``bytes``
+        (some may be empty).  key_idx: (m,) key per item; None: item i uses key
+        i (m <= nkeys); an index >= nkeys gives 64 zero bytes.  Returns (m, 64)
+        uint8, R || s."""
+        from .verifier import pack_msgs
+        buf, offsets = pack_msgs(msgs)
+        m = offsets.size - 1
+        idx = None if key_idx is None else np.ascontiguousarray(key_idx, np.uint32).reshape(-1)
+        if idx is not None and idx.size != m:
+            raise ValueError("key_idx and msgs differ in length")
+        out = np.zeros((m, 64), np.uint8)
+        if m:
+            _lib.check(self._lib.hsv_signer_sign_msgs(self._h, None if idx is None else _ptr(idx), _ptr(buf),
+                                                      _ptr(offsets), 0, 0, m, _ptr(out)), "hsv_signer_sign_msgs")
+        return out
+
+    def sign_msgs_device(self, msgs, sig, offsets=None, msg_len: int = 0, msg_stride=None, key_idx=None,
+                         stream=None, fault=None) -> None:
+        """Device tensors, enqueued on ``stream`` (default: torch's current
+        stream), no synchronisation (hsv_signer_sign_msgs_device).  msgs: the
+        message bytes at any alignment (None when every message is empty);
+        offsets: an int64 tensor of m + 1 byte offsets into it, or None for
+        ``msg_len`` bytes per item at ``msg_stride`` (default msg_len; 0 = one
+        shared message) -- the conventions of ``verifier.verify_msgs_device``.
+        sig: (m, >= 64) uint8 rows whose address and stride are multiples of
+        16; key_idx: (m,) int32 / uint32 or None; fault: optional per-call
+        fault words (``sign_device``).  An item whose offsets decrease, or whose
+        key index is out of range, gets 64 zero bytes."""
+        from .verifier import _fault_ptr
+        import torch
+        m = sig.shape[0]
+        for t in (msgs, offsets, key_idx, fault):
+            if t is not None and t.device != sig.device:
+                raise ValueError(f"all tensors must live on {sig.device}, got {t.device}")
+        if offsets is not None and offsets.numel() != m + 1:
+            raise ValueError("one message per item (m + 1 offsets)")
+        if key_idx is not None and key_idx.numel() != m:
+            raise ValueError("key_idx and sig differ in length")
+        if msg_stride is None:
+            msg_stride = msg_len
+        with torch.cuda.device(sig.device):
+            if stream is None:
+                stream = torch.cuda.current_stream(sig.device).cuda_stream
+            rc = self._lib.hsv_signer_sign_msgs_device(
+                self._h, ctypes.c_void_p(key_idx.data_ptr()) if key_idx is not None else None,
+                ctypes.c_void_p(msgs.data_ptr()) if msgs is not None else None,
+                ctypes.c_void_p(offsets.data_ptr()) if offsets is not None else None, msg_len, msg_stride, m,
+                ctypes.c_void_p(sig.data_ptr()), sig.stride(0), _fault_ptr(fault), ctypes.c_void_p(stream))
+        _lib.check(rc, "hsv_signer_sign_msgs_device")
 
     def sign_transactions(self, txs, key_idx=None, offsets=None) -> np.ndarray:
         """Mempool transactions ``message || pk || R || s`` (hsv_signer_sign_transactions):

@@ -239,3 +239,41 @@ def transactions_gpu(n: int, tx_size: int = 512, seed: int = 0) -> TxWorkload:
     with Signer(seeds) as s:
         txs = s.sign_transactions(txs)
     return TxWorkload(txs, np.ones(n, bool), np.full(n, -1, np.int8), np.ones(n, bool))
+
+
+def messages_gpu(lens, seed: int = 0):
+    """Whole messages of the given byte lengths (some may be 0), one fresh key
+    per item, signed on the GPU in one `Signer.sign_msgs_device` call -- the
+    input of `verifier.verify_msgs_device`, without a host signing loop.
+    Returns device tensors ``(pk (n, 32), sig (n, 64), buf, offsets (n + 1,)
+    int64)``, message i = buf[offsets[i]:offsets[i + 1]]; seeded.  Every item
+    is honest.  Raises HsvLibraryError (HSV_ERR_NO_DEVICE) without a GPU."""
+    from .signer import Signer
+    lens = np.ascontiguousarray(lens, np.int64).reshape(-1)
+    if lens.size and int(lens.min()) < 0:
+        raise ValueError("negative message length")
+    n = lens.size
+    rng = np.random.default_rng(seed)
+    seeds = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+    offsets = np.zeros(n + 1, np.int64)
+    np.cumsum(lens, out=offsets[1:])
+    buf = rng.integers(0, 256, size=int(offsets[-1]), dtype=np.uint8)
+    with Signer(seeds) as s:
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        pk = torch.from_numpy(s.public_keys()).to(dev)
+        d_buf = torch.from_numpy(buf).to(dev)
+        d_offsets = torch.from_numpy(offsets).to(dev)
+        sig = torch.zeros((n, 64), dtype=torch.uint8, device=dev)
+        fault = torch.zeros(2, dtype=torch.int32, device=dev)
+        if n:
+            s.sign_msgs_device(d_buf if d_buf.numel() else None, sig, offsets=d_offsets, fault=fault)
+        torch.cuda.synchronize(dev)
+        if int(fault[0]):
+            raise _lib_error("HSV_ERR_DEVICE_FAULT: messages_gpu: a signature failed the device self-check")
+    return pk, sig, d_buf, d_offsets
+
+
+def _lib_error(text: str):
+    from . import _lib
+    return _lib.HsvLibraryError(text)

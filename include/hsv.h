@@ -525,6 +525,47 @@ HSV_API int hsv_signer_sign_transactions(hsv_signer *s, const uint32_t *key_idx,
 HSV_API int hsv_signer_sign_transactions_device(const hsv_signer *s, const uint32_t *d_key_idx, uint8_t *d_txs,
                                                 const uint64_t *d_offsets, size_t tx_size, size_t n,
                                                 uint32_t *d_fault, void *stream);
+/* Sign whole messages whose lengths differ: the signing mirror of
+ * hsv_verify_msgs*, which is the verifying half of this call.  Addressing is
+ * hsv_verify_msgs*'s, keys and outputs are hsv_signer_sign*'s:
+ * offsets != NULL: message i is msgs[offsets[i] .. offsets[i+1]) (m+1 entries,
+ *                  relative to msgs).
+ * offsets == NULL: message i is msg_len bytes at msgs + i*msg_stride
+ *                  (msg_stride 0: one shared message; a non-zero stride below
+ *                  msg_len is HSV_ERR_INVALID_ARG).
+ * A message may be empty.  msgs may have any alignment, and may be NULL when
+ * every message is empty.  key_idx == NULL: item i uses key i (m <= nkeys,
+ * else HSV_ERR_INVALID_ARG); otherwise key key_idx[i], and an index >= nkeys
+ * writes 64 zero bytes and raises no fault.  sig_out: m*64 B, R || s, bit-exact
+ * with hsv_sign(seed, M, len).  As the rest of the signer this path is
+ * NOT constant time: it is for load generation and input synthesis only, never
+ * for a key that matters.
+ * Host form: synchronous, on the signer's device; m == 0 does nothing.
+ * Decreasing offsets return HSV_ERR_INVALID_ARG (hsv_last_error names the
+ * item) before any device work and before a byte of sig_out is written; a
+ * failed device self-check returns HSV_ERR_DEVICE_FAULT (that item: 64 zero
+ * bytes).  There is no CPU fallback (HSV_ERR_NO_DEVICE without a GPU).  Plain
+ * staged copies on one device, at most 2^22 items and 2^29 message bytes per
+ * round: this call is neither pipelined nor sharded across GPUs. */
+HSV_API int hsv_signer_sign_msgs(hsv_signer *s, const uint32_t *key_idx, const uint8_t *msgs,
+                                 const uint64_t *offsets, size_t msg_len, size_t msg_stride,
+                                 size_t m, uint8_t *sig_out);
+/* Device-resident, stream-ordered form (device = the signer's: buffers or a
+ * stream of another device are HSV_ERR_INVALID_ARG); never synchronises.
+ * d_sig and sig_stride must be multiples of 16, d_key_idx 4-byte and d_offsets
+ * 8-byte aligned (HSV_ERR_ALIGN, checked before anything else is looked at);
+ * sig_stride >= 64.  An item whose offsets decrease gets 64 zero bytes and no
+ * fault; its neighbours are unaffected.  d_fault (optional) as
+ * hsv_signer_sign_device: only d_fault[0] is ever set, by an item whose [r]B
+ * fails the self-check; that item gets 64 zero bytes.  Batches above 2^22
+ * items run as 2^22-item rounds, in order on `stream`.  A round is three
+ * kernels: the nonces r = SHA-512(prefix || M), the points R = [r]B, the
+ * responses s = r + SHA-512(R || pk || M) a. */
+HSV_API int hsv_signer_sign_msgs_device(const hsv_signer *s, const uint32_t *d_key_idx,
+                                        const uint8_t *d_msgs, const uint64_t *d_offsets,
+                                        size_t msg_len, size_t msg_stride, size_t m,
+                                        uint8_t *d_sig, size_t sig_stride, uint32_t *d_fault,
+                                        void *stream);
 
 /* Synthesis helper for the corrupted-input mixes (SURVEY 8(d) C3/C4 "mixed-
  * order A"; Appendix A.3 rows 7-8): the key A' = [a]B + [2*torsion+1]T8 (a

@@ -457,6 +457,36 @@ class Signer {
                                                             stream),
                         "hsv_signer_sign_transactions_device");
   }
+  // Whole messages of differing lengths (hsv_signer_sign_msgs, the signing
+  // mirror of hsv_verify_msgs): message i is msgs[offsets[i] .. offsets[i+1])
+  // (m + 1 offsets), or msg_len bytes at msgs + i * msg_stride when offsets is
+  // nullptr; key key_idx[i] for item i (nullptr: key i).  Returns m * 64
+  // bytes, R || s; decreasing offsets throw before anything is signed.
+  std::vector<uint8_t> sign_msgs(const uint32_t *key_idx, const uint8_t *msgs, const uint64_t *offsets,
+                                 size_t msg_len, size_t msg_stride, size_t m) {
+    std::vector<uint8_t> sig(m * 64);
+    crypto::check_infra(hsv_signer_sign_msgs(h_, key_idx, msgs, offsets, msg_len, msg_stride, m, sig.data()),
+                        "hsv_signer_sign_msgs");
+    return sig;
+  }
+  // one message per item, item i with key i
+  std::vector<uint8_t> sign_msgs(const std::vector<std::vector<uint8_t>> &msgs) {
+    std::vector<uint64_t> offsets(msgs.size() + 1, 0);
+    std::vector<uint8_t> buf;
+    for (size_t i = 0; i < msgs.size(); ++i) {
+      buf.insert(buf.end(), msgs[i].begin(), msgs[i].end());
+      offsets[i + 1] = buf.size();
+    }
+    return sign_msgs(nullptr, buf.empty() ? nullptr : buf.data(), offsets.data(), 0, 0, msgs.size());
+  }
+  // device-resident, stream-ordered form (hsv_signer_sign_msgs_device)
+  void sign_msgs_device(const uint32_t *d_key_idx, const uint8_t *d_msgs, const uint64_t *d_offsets, size_t msg_len,
+                        size_t msg_stride, size_t m, uint8_t *d_sig, size_t sig_stride, uint32_t *d_fault = nullptr,
+                        void *stream = nullptr) const {
+    crypto::check_infra(hsv_signer_sign_msgs_device(h_, d_key_idx, d_msgs, d_offsets, msg_len, msg_stride, m, d_sig,
+                                                    sig_stride, d_fault, stream),
+                        "hsv_signer_sign_msgs_device");
+  }
   hsv_signer *handle() const { return h_; }
 
  private:

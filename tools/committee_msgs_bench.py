@@ -3,7 +3,8 @@
 hsv_verify_msgs_device on the same bytes.
 
 Workload: n (default 2^20) device-resident items, signed on the GPU by
-Signer.sign_device with K keys drawn uniformly per item, for K = 4, 100 and
+Signer.sign_device (the ragged shape: by one Signer.sign_msgs_device call over
+the packed buffer) with K keys drawn uniformly per item, for K = 4, 100 and
 1000, in three shapes: msg_len 32, msg_len 416 (the message part of the
 reference benchmark's 512-byte transaction) and ragged lengths uniform in
 0 .. 1024 packed back to back in random order.  The reference measures this
@@ -69,20 +70,16 @@ def signed_items(torch, signer, shape, n, key_idx, rnd, gen, dev):
         d_msgs = torch.randint(0, 256, (n, length), generator=gen, dtype=torch.uint8).to(dev)
         signer.sign_device(d_msgs, d_sig, key_idx=key_idx, msg_len=length)
         return d_sig, d_msgs.view(-1), {"msg_len": length}, key_idx
+    # the messages back to back in random order, signed in one sign_msgs_device call
     lens = np.sort(rnd.integers(0, 1025, n))
-    d_pad = torch.randint(0, 256, (n, 1024), generator=gen, dtype=torch.uint8).to(dev)
-    starts = np.searchsorted(lens, np.arange(1026))
-    for length in range(1025):                       # items of one length are consecutive rows: one launch each
-        lo, hi = int(starts[length]), int(starts[length + 1])
-        if hi > lo:
-            signer.sign_device(d_pad[lo:hi], d_sig[lo:hi], key_idx=key_idx[lo:hi], msg_len=length)
     perm = torch.from_numpy(rnd.permutation(n)).to(dev)
     d_lens = torch.from_numpy(lens).to(dev)[perm]
-    mask = torch.arange(1024, device=dev)[None, :] < d_lens[:, None]
-    d_buf = d_pad[perm][mask]                        # row-major: the messages back to back, in perm order
     d_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
     d_off[1:] = torch.cumsum(d_lens, 0)
-    return d_sig[perm].contiguous(), d_buf, {"offsets": d_off}, key_idx[perm].contiguous()
+    d_buf = torch.randint(0, 256, (int(d_off[-1]),), generator=gen, dtype=torch.uint8).to(dev)
+    key_idx = key_idx[perm].contiguous()
+    signer.sign_msgs_device(d_buf, d_sig, offsets=d_off, key_idx=key_idx)
+    return d_sig, d_buf, {"offsets": d_off}, key_idx
 
 
 def main():

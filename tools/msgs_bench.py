@@ -148,23 +148,20 @@ def main():
     del d_m416, d_tx
 
     # ---- ragged: lengths uniform in 0..1024, random order ---------------------
+    # item j is signed by key perm[j]: one sign_msgs_device call over the packed buffer
     lens = np.sort(rnd.integers(0, 1025, n))
-    d_pad = torch.from_numpy(rnd.integers(0, 256, (n, 1024), dtype=np.uint8)).to(dev)
-    d_sr = torch.zeros((n, 64), dtype=torch.uint8, device=dev)
-    d_idx = torch.arange(n, dtype=torch.int32, device=dev)
-    starts = np.searchsorted(lens, np.arange(1026))
-    for length in range(1025):                       # items of one length are consecutive rows: one launch each
-        lo, hi = int(starts[length]), int(starts[length + 1])
-        if hi > lo:
-            signer.sign_device(d_pad[lo:hi], d_sr[lo:hi], key_idx=d_idx[lo:hi], msg_len=length)
     perm = torch.from_numpy(rnd.permutation(n)).to(dev)
     d_lens = torch.from_numpy(lens).to(dev)[perm]
-    mask = torch.arange(1024, device=dev)[None, :] < d_lens[:, None]
-    d_buf = d_pad[perm][mask]                        # row-major: the messages back to back, in perm order
     d_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
     d_off[1:] = torch.cumsum(d_lens, 0)
-    d_pkr, d_sr = d_pk[perm].contiguous(), d_sr[perm].contiguous()
-    del d_pad, mask
+    gen = torch.Generator(device=dev).manual_seed(args.seed)
+    d_buf = torch.randint(0, 256, (int(d_off[-1]),), dtype=torch.uint8, device=dev, generator=gen)
+    d_sr = torch.zeros((n, 64), dtype=torch.uint8, device=dev)
+    signer.sign_msgs_device(d_buf, d_sr, offsets=d_off, key_idx=perm.to(torch.int32), fault=fault)
+    torch.cuda.synchronize()
+    if fault.cpu().tolist() != [0, 0]:
+        raise SystemExit(f"msgs_bench: signing the ragged batch: device self-check words {fault.cpu().tolist()}")
+    d_pkr = d_pk[perm].contiguous()
     ragged = lambda: verifier.verify_msgs_device(d_pkr, d_sr, d_buf, d_off, flags=flags)
     verifier.verify_msgs_device(d_pkr, d_sr, d_buf, d_off, flags=flags, fault=fault)
     all_strict_ok(torch, flags, fault, "ragged")

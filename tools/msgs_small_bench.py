@@ -49,7 +49,7 @@ def main():
     args = ap.parse_args()
 
     import torch
-    from hsverify import _lib, _testing, verifier
+    from hsverify import Signer, _lib, _testing, verifier
 
     if _lib.device_count() <= 0:
         raise SystemExit("msgs_small_bench: no HIP device visible (there is no CPU form of the verifier)")
@@ -105,16 +105,20 @@ def main():
             msgs = rnd.integers(0, 256, (nmax, length), dtype=np.uint8)
             pk, sig = verifier.sign_many(seeds, msgs)
             kinds[f"len{length}"] = (pk, sig, msgs.reshape(-1), None, length)
+        # ragged: the packed buffer signed on the GPU in one call (Signer.sign_msgs_device)
         lens = rnd.integers(0, 1025, nmax)
-        pad = rnd.integers(0, 256, (nmax, 1024), dtype=np.uint8)
-        pk = np.zeros((nmax, 32), np.uint8)
-        sig = np.zeros((nmax, 64), np.uint8)
-        for length in np.unique(lens):
-            idx = np.nonzero(lens == length)[0]
-            pk[idx], sig[idx] = verifier.sign_many(seeds[idx], np.ascontiguousarray(pad[idx, :length]))
         off = np.zeros(nmax + 1, np.int64)
         off[1:] = np.cumsum(lens)
-        kinds["ragged_0_1024"] = (pk, sig, pad[np.arange(1024)[None, :] < lens[:, None]], off, 0)
+        buf = rnd.integers(0, 256, int(off[-1]), dtype=np.uint8)
+        with Signer(seeds) as signer:
+            d_sig = torch.zeros((nmax, 64), dtype=torch.uint8, device=dev)
+            fault = torch.zeros(2, dtype=torch.int32, device=dev)
+            signer.sign_msgs_device(torch.from_numpy(buf).to(dev), d_sig, offsets=torch.from_numpy(off).to(dev),
+                                    fault=fault)
+            torch.cuda.synchronize()
+            if fault.cpu().tolist() != [0, 0]:
+                raise SystemExit(f"msgs_small_bench: signing the ragged batch: self-check words {fault.cpu().tolist()}")
+            kinds["ragged_0_1024"] = (signer.public_keys(), d_sig.cpu().numpy(), buf, off, 0)
 
         rec = {"what": "tools/msgs_small_bench.py: hsv_verify_msgs_device, default route (a small form, one launch) "
                        "against two launches (hsv_test_msgs_small 0), one process, alternating blocks",
