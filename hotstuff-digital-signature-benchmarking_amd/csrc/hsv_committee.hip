@@ -95,7 +95,7 @@ __device__ __forceinline__ void comb_verify_lane(const uint32_t *__restrict__ ke
                   reinterpret_cast<const uint4 *>(sig + (uint64_t)i * sig_stride),
                   reinterpret_cast<const uint4 *>(msg + (uint64_t)i * msg_stride), pkw, sigw, msgw);
   const uint32_t f = verify_comb<DIGITS>(pkw, key_flags[kk], sigw, msgw, key_tables[kk], tb, inject);
-  if (f & kFault) fault[0] = 1u;  // device self-check (hsv_kernels.hip report_faults)
+  if (f & kFault) fault[0] = 1u;  // device self-check (hsv_pointpass.hpp report_faults)
   flags_out[i] = kvalid ? (uint8_t)f : (uint8_t)0;
 }
 
@@ -416,7 +416,7 @@ __device__ __forceinline__ void comb_quad_block(const uint32_t *__restrict__ key
                      (small_a ? kSmallA : 0u) | (small_r ? kSmallR : 0u) | (s_ok ? kSOk : 0u) |
                      (a_ok ? kAOk : 0u) | (r_ok ? kROk : 0u);
   const uint32_t fb = a_ok & r_ok & (sane ^ 1u);
-  if (fb | ((rf >> 2) & 1u)) fault[0] = 1u;  // device self-check (hsv_kernels.hip report_faults)
+  if (fb | ((rf >> 2) & 1u)) fault[0] = 1u;  // device self-check (hsv_pointpass.hpp report_faults)
   if (valid && g == 0u) flags_out[i0] = kvalid ? (uint8_t)f : (uint8_t)0;
   HSV_QC_CLK(5);
 #ifdef HSV_QC_WAVE_CLOCKS

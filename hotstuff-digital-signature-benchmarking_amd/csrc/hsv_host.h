@@ -198,7 +198,7 @@ int slot_pipeline(Slot &s);  // stream2, the copy stream, the events of run_pipe
 // the slot's coherent sync region (Slot::h_sync) of at least `bytes`
 int slot_sync_region(Slot &s, size_t bytes);
 
-// Device self-check words (hsv_kernels.hip report_faults): two words per
+// Device self-check words (hsv_pointpass.hpp report_faults): two words per
 // launch, zeroed before it; non-zero after it -> HSV_ERR_DEVICE_FAULT.
 constexpr size_t kFaultBytes = 8;
 int check_faults(const uint8_t *words, const char *where);

@@ -41,7 +41,7 @@ int hsvi_variant_list(int *out, int cap);  // ids built into this library; retur
 int hsvi_variant_available(int variant);
 // fault: two device-visible words the caller zeroed before the launch; the
 // kernels set fault[0] (an item's final point failed the self-check) and
-// fault[1] (a workspace canary changed) -- see hsv_kernels.hip report_faults.
+// fault[1] (a workspace canary changed) -- see hsv_pointpass.hpp report_faults.
 // Required (non-null) for the product variants.
 hipError_t hsv_launch_verify(int variant, const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig,
                              uint64_t sig_stride, const uint8_t *msg, uint64_t msg_stride,
@@ -65,9 +65,23 @@ int hsvi_set_inject(int mode);
 // previous bound or -1.
 int hsvi_set_lattice_bits(int bits);
 // The bound in force, and a fresh canary nonce (odd, never 0): what launch_hp
-// hands its kernels, for the point-pass launcher of hsv_mempool.hip.
+// hands its kernels, for the launchers of hsv_small.hip and hsv_mempool.hip.
 int hsvi_lattice_bits(void);
 uint32_t hsvi_next_nonce(void);
+// The one-launch latency forms (hsv_small.hip), which hsv_launch_verify* and
+// hsv_launch_verify_msgs take at n <= hsv::kPairMax items: quad, joint, row or
+// pair by n.  Arguments as the entry point's; comb16: the wide comb of B.
+// hsv_small_ws_bytes(n): the workspace the digest launch needs.  force: 0 the
+// form by n, 1..kSmallForms that form at any n; *form_id: the form launched.
+hipError_t hsv_launch_small(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, uint64_t sig_stride,
+                            const uint8_t *msg, uint64_t msg_stride, uint32_t n, uint8_t *flags_out,
+                            uint32_t *strict_bits, const uint32_t *comb16, uint32_t *fault, void *ws, size_t ws_cap,
+                            hipStream_t stream);
+size_t hsv_small_ws_bytes(uint32_t n);
+hipError_t hsv_launch_small_msgs(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, uint64_t sig_stride,
+                                 const uint8_t *msgs, const uint64_t *offsets, uint64_t msg_len, uint64_t msg_stride,
+                                 uint32_t n, uint8_t *flags_out, uint32_t *strict_bits, const uint32_t *comb16,
+                                 uint32_t *fault, int force, int *form_id, hipStream_t stream);
 // Row-form field arithmetic against the one-lane form (hsv_committee.hip).
 int hsvi_lanesplit_check(const uint32_t *in, uint32_t rows, uint32_t *out);
 // Read-and-clear of two device fault words in one atomic exchange each, on
@@ -87,6 +101,11 @@ double hsv_launch_mad_peak(int device_cus);
 
 #ifdef __cplusplus
 namespace hsv {
+// The latency forms at or below this many items, the two-pass kernels above;
+// the forms' ids are 1..kSmallForms (quad, joint, row, pair).
+constexpr uint32_t kPairMax = 1u << 13;
+constexpr int kSmallForms = 4;
+
 // A launcher's workspace: the caller's when it holds `need` bytes (a pipeline
 // that keeps one per stream), else a block from the library pool, which
 // done() frees on the stream.

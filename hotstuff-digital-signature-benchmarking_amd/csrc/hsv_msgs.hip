@@ -14,7 +14,7 @@
 // Two ordinary launches above 2^13 items and no inter-workgroup waiting: a
 // message of many megabytes keeps one wave of the prepass busy and nothing
 // polls for it.  At or below 2^13 items the small forms of
-// hsv_kernels.hip run instead, one launch, their prepass wave hashing through
+// hsv_small.hip run instead, one launch, their prepass wave hashing through
 // the same msg_hash_lane.
 #include <hip/hip_runtime.h>
 

@@ -1,7 +1,8 @@
-// The point pass's shared pieces (hsv_kernels.hip: hsv_verify_hp_kernel and
-// the latency forms; hsv_mempool.hip: the fused transaction launch): the
-// per-lane table store, record loads, work counters and the device
-// self-check words.
+// The point pass's shared pieces (hsv_kernels.hip: hsv_verify_hp_kernel;
+// hsv_small.hip: the latency forms; hsv_mempool.hip: the fused transaction
+// launch; hsv_routed.hpp: the routed rounds): the per-lane table store, record
+// loads, the verdict store, a fallback item's full-length path, work counters
+// and the device self-check words.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -141,6 +142,46 @@ __device__ __forceinline__ void load_triple(const uint8_t *pk, uint64_t pk_strid
   sigw[12] = s3.x; sigw[13] = s3.y; sigw[14] = s3.z; sigw[15] = s3.w;
   msgw[0] = m0.x; msgw[1] = m0.y; msgw[2] = m0.z; msgw[3] = m0.w;
   msgw[4] = m1.x; msgw[5] = m1.y; msgw[6] = m1.z; msgw[7] = m1.w;
+}
+
+// 32 bytes (16-byte aligned) into eight words
+__device__ __forceinline__ void load_words8(const uint8_t *p, uint32_t w[8]) {
+  const uint4 *q = reinterpret_cast<const uint4 *>(p);
+  const uint4 a = q[0], b = q[1];
+  w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
+  w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
+}
+
+// item i's verdict through either output: the flag byte, the STRICT_OK bit
+__device__ __forceinline__ void store_verdict(uint8_t *flags_out, uint32_t *strict_bits, uint32_t i, uint32_t f) {
+  if (flags_out) flags_out[i] = (uint8_t)f;
+  if (strict_bits && (f & kStrictOk)) atomicOr(&strict_bits[i >> 5], 1u << (i & 31u));
+}
+
+// The full-length path of item i, a fallback item (no short lattice pair).
+// KREC = false: k is hashed here from R || A || the 32 bytes at msg + i *
+// msg_stride.  KREC = true (whole messages: the prepass hashed them, and msg,
+// of whatever type, is never touched): k mod l is words 10..17 of the item's
+// prepass record (rec = the item's column, row stride `stride`).
+template <int WA, int CB, bool KREC, class M, class VT>
+__device__ __forceinline__ uint32_t verify_fallback_item(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig,
+                                                         uint64_t sig_stride, M msg, uint64_t msg_stride,
+                                                         uint32_t i, const uint32_t *rec, uint64_t stride,
+                                                         const uint32_t *tb, VT &vt) {
+  uint32_t pkw[8], sigw[16];
+  if constexpr (KREC) {
+    load_words8(pk + (uint64_t)i * pk_stride, pkw);
+    load_words8(sig + (uint64_t)i * sig_stride, sigw);
+    load_words8(sig + (uint64_t)i * sig_stride + 32, sigw + 8);
+    sc k;
+    HSV_UNROLL
+    for (int j = 0; j < 8; ++j) k.v[j] = rec[(uint64_t)(10 + j) * stride];
+    return verify_one_full_comb<WA, false, CB>(pkw, sigw, k, tb, vt);
+  } else {
+    uint32_t msgw[8];
+    load_triple(pk, pk_stride, sig, sig_stride, msg, msg_stride, i, pkw, sigw, msgw);
+    return verify_one_full_comb<WA, false, CB>(pkw, sigw, msgw, tb, vt);
+  }
 }
 
 // Work counters of the comb kernels, zeroed before the launch (32 bytes).

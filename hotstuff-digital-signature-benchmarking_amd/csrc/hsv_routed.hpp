@@ -49,18 +49,7 @@ __device__ __forceinline__ uint32_t mask_rank(uint64_t mask, uint32_t lane) {
   return (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
 }
 
-__device__ __forceinline__ void load_words8(const uint8_t *p, uint32_t w[8]) {
-  const uint4 *q = reinterpret_cast<const uint4 *>(p);
-  const uint4 a = q[0], b = q[1];
-  w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
-  w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-}
-
-// item i's verdict through either output: the flag byte, the STRICT_OK bit
-__device__ __forceinline__ void store_verdict(uint8_t *flags_out, uint32_t *strict_bits, uint32_t i, uint32_t f) {
-  if (flags_out) flags_out[i] = (uint8_t)f;
-  if (strict_bits && (f & kStrictOk)) atomicOr(&strict_bits[i >> 5], 1u << (i & 31u));
-}
+// (load_words8 and store_verdict, which the pass bodies use, are in hsv_pointpass.hpp)
 
 // ---- the host side of a round ----------------------------------------------------
 // (internal linkage: each of the two files caches the occupancy of its own

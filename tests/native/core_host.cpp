@@ -44,7 +44,7 @@ struct HostBTab {
 };
 
 // per-lane variable-base tables (the kernel keeps them in a global-memory slot)
-// inject: the kernel's fault injection (GlobalVarTab::put, hsv_kernels.hip)
+// inject: the kernel's fault injection (GlobalVarTab::put, hsv_pointpass.hpp)
 struct HostVarTab {
   uint32_t e[2][17][32];
   uint32_t inject = kInjectNone;

@@ -106,7 +106,7 @@ def test_reproducer_double_store_loop_is_divergent(hipcc):
     assert list(wp.values()) == [False], "lanes-0/1 store: expected a uniform work loop"
 
 
-@pytest.mark.parametrize("src", ["hsv_kernels.hip", "hsv_committee.hip", "hsv_mempool.hip"])
+@pytest.mark.parametrize("src", ["hsv_kernels.hip", "hsv_small.hip", "hsv_committee.hip", "hsv_mempool.hip"])
 def test_product_work_loops_are_uniform(hipcc, src):
     """Every product kernel that deals batches from an atomic counter keeps its
     work loop uniform (no exec-masked back edge)."""

@@ -1,5 +1,5 @@
 """ISA-level checks of the message instantiations of the four small-batch
-kernels (hsv_kernels.hip; no GPU: hipcc -S only).
+kernels (hsv_small.hip; no GPU: hipcc -S only).
 
 Each small form -- quad, joint, row, pair -- is compiled twice: for a 32-byte
 digest (the form hsv_verify_device takes) and for whole messages (MSG = true,
@@ -23,17 +23,17 @@ FORMS = ("hsv_verify_quad_kernel", "hsv_verify_joint_kernel", "hsv_verify_row_ke
 
 @pytest.fixture(scope="module")
 def asm():
-    """hsv_kernels.hip's gfx950 assembly.  tests/test_kernel_isa.py compiles the
+    """hsv_small.hip's gfx950 assembly.  tests/test_kernel_isa.py compiles the
     same file with the same flags; when its output is newer than every source
     it is read instead of spending the compile (minutes) a second time."""
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not available")
-    done = os.path.join(OUT, "hsv_kernels.hip.s")
+    done = os.path.join(OUT, "hsv_small.hip.s")
     srcs = [os.path.join(d, f) for d in (os.path.join(PKG, "csrc"), os.path.join(ROOT, "include"))
             for f in os.listdir(d)]
     if os.path.exists(done) and os.path.getmtime(done) > max(os.path.getmtime(s) for s in srcs):
         return open(done).read().split("\n")
-    return _compile(os.path.join(PKG, "csrc", "hsv_kernels.hip"), "hsv_kernels.hip.s")
+    return _compile(os.path.join(PKG, "csrc", "hsv_small.hip"), "hsv_small.hip.s")
 
 
 def resources(lines):
