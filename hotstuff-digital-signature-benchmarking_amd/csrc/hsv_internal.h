@@ -84,6 +84,12 @@ hipError_t hsv_launch_small_msgs(const uint8_t *pk, uint64_t pk_stride, const ui
                                  uint32_t *fault, int force, int *form_id, hipStream_t stream);
 // Row-form field arithmetic against the one-lane form (hsv_committee.hip).
 int hsvi_lanesplit_check(const uint32_t *in, uint32_t rows, uint32_t *out);
+// The one-lane field, scalar and lattice primitives on raw operands
+// (hsv_test_prims.hip, linked into libhsv_test.so only): n records of
+// hsv::kPrimFieldIn / kPrimScalarIn words in, kPrimFieldOut / kPrimScalarOut
+// words out (hsv_test_prims.hpp), host buffers; 0 or a hipError_t.
+int hsvi_test_field_ops(const uint32_t *in, uint32_t n, uint32_t *out);
+int hsvi_test_scalar_ops(const uint32_t *in, uint32_t n, uint32_t *out);
 // Read-and-clear of two device fault words in one atomic exchange each, on
 // `stream`: out (device memory, 2 words) receives the old values.
 hipError_t hsv_launch_fault_exchange(uint32_t *words, uint32_t *out, hipStream_t stream);

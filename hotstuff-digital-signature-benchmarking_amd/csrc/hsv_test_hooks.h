@@ -1,8 +1,9 @@
 /*
  * hsv_test_hooks.h -- test and measurement hooks of libhsv_test.so.
  *
- * libhsv_test.so is libhsv.so's object files plus csrc/hsv_test_hooks.cpp:
- * the same kernels and host code, and in addition the hooks below.  The
+ * libhsv_test.so is libhsv.so's object files plus csrc/hsv_test_hooks.cpp and
+ * the test kernels of csrc/hsv_test_prims.hip: the same product kernels and
+ * host code, and in addition the hooks below.  The
  * product library exports none of them (tests/test_capi.py checks its
  * dynamic symbols against include/hsv.h), so no stray call can change the
  * behaviour of a deployed process.  tests/ and tools/ load libhsv_test.so
@@ -29,6 +30,14 @@ HSV_API int hsv_test_inject_mode(void);
 HSV_API int hsv_test_corrupt_auto_committee(void);
 /* Row-form field arithmetic against the one-lane form (tests/test_lanesplit.py). */
 HSV_API int hsv_test_lanesplit_check(const uint32_t *in, uint32_t rows, uint32_t *out);
+/* The device's one-lane field arithmetic (hsv_fe26x10.hpp, its inline-asm
+ * branch) and its mod-l and lattice routines on raw operands, one item per
+ * lane (csrc/hsv_test_prims.hpp has the op codes and the record layout; the
+ * same text runs on the host in tests/native/prims_host.cpp).  in: n records
+ * of 24 (field) or 32 (scalar) words; out: n records of 24 or 16 words, all
+ * host memory.  0, or a hipError_t (tests/test_prims_gpu.py). */
+HSV_API int hsv_test_field_ops(const uint32_t *in, uint32_t n, uint32_t *out);
+HSV_API int hsv_test_scalar_ops(const uint32_t *in, uint32_t n, uint32_t *out);
 /* Lattice bound of the comb-path prepass (0 = default 138; 133 sends the
  * lattice-fallback fixtures down the full-length path); previous bound or -1. */
 HSV_API int hsv_set_lattice_bits(int bits);

@@ -30,7 +30,8 @@ HOOKS = ("hsv_test_inject_fault", "hsv_test_inject_mode", "hsv_test_corrupt_auto
          "hsv_test_resident_counts", "hsv_test_resident_post_bad", "hsv_test_tx_records",
          "hsv_test_pipe_schedule", "hsv_test_numa_plan", "hsv_test_pinned_thread_cpus", "hsv_test_signer_group",
          "hsv_test_tx_sign_chunk", "hsv_test_msg_sign_chunk", "hsv_test_stage_bytes", "hsv_test_committee_tx_counts",
-         "hsv_test_committee_msgs_counts", "hsv_test_msgs_small", "hsv_test_msgs_form_counts")
+         "hsv_test_committee_msgs_counts", "hsv_test_msgs_small", "hsv_test_msgs_form_counts",
+         "hsv_test_field_ops", "hsv_test_scalar_ops")
 
 # flag bits (include/hsv.h)
 STRICT_OK = 0x01
@@ -141,6 +142,8 @@ def _declare(lib):
         "hsv_test_inject_mode": (ctypes.c_int, []),
         "hsv_test_corrupt_auto_committee": (ctypes.c_int, []),
         "hsv_test_lanesplit_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+        "hsv_test_field_ops": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+        "hsv_test_scalar_ops": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
         "hsv_host_call_stats": (None, [ctypes.POINTER(ctypes.c_double)] * 3),
         "hsv_host_call_marks": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.c_int]),
         "hsv_pack_threads": (ctypes.c_int, []),

@@ -115,6 +115,31 @@ def lanesplit_check(words):
     return out
 
 
+def _prim_ops(name, records, win, wout):
+    import numpy as np
+    w = np.ascontiguousarray(records, dtype=np.uint32)
+    if w.ndim != 2 or w.shape[1] != win:
+        raise ValueError(f"{name}: records must be an (n, {win}) uint32 array")
+    out = np.zeros((len(w), wout), np.uint32)
+    rc = _lib.hook(name)(ctypes.c_void_p(w.ctypes.data), ctypes.c_uint32(len(w)), ctypes.c_void_p(out.ctypes.data))
+    if rc != 0:
+        raise RuntimeError(f"{name} failed: hipError {rc}")
+    return out
+
+
+def field_ops(records):
+    """The device's one-lane field arithmetic on raw limbs, one record per lane
+    in one launch (hsv_test_field_ops; layout and op codes in
+    csrc/hsv_test_prims.hpp): (n, 24) uint32 in, (n, 24) uint32 out."""
+    return _prim_ops("hsv_test_field_ops", records, 24, 24)
+
+
+def scalar_ops(records):
+    """The device's mod-l and lattice routines, one record per lane in one
+    launch (hsv_test_scalar_ops): (n, 32) uint32 in, (n, 16) uint32 out."""
+    return _prim_ops("hsv_test_scalar_ops", records, 32, 16)
+
+
 def committee_tx_counts() -> tuple:
     """(hits, misses, fallback items) of the calling thread's last
     Committee.verify_transactions* call, summed over its rounds (test library;
