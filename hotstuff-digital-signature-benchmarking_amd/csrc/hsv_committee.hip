@@ -26,6 +26,7 @@
 #include "hsv_comb.hpp"
 #include "hsv_fe16x16.hpp"
 #include "hsv_internal.h"
+#include "hsv_quad.hpp"
 
 namespace hsv {
 
@@ -128,27 +129,15 @@ hsv_comb_verify_kernel(const uint32_t *__restrict__ key_idx, const uint8_t *__re
 // lane-count switch and the other closed latency-form experiments of rounds
 // 3-4 -- one-lane R, one row per R, the hash on the comb wave or on every
 // lane, one-lane final checks, compact root-chain and SHA-512 bodies -- were
-// removed in round 5; they are in git history at 5c186e7.)
-constexpr int kCombLanes = 16;
-constexpr int kCombPosPerLane = kCombPos / kCombLanes;
+// removed in round 5; they are in git history at 5c186e7.)  The geometry's
+// constants (kCombLanes = L, kFusedVotes, the waves' roles) and the two lane
+// helpers are in hsv_quad.hpp, shared with hsv_cmsg_quad_kernel.
 
 // Checks of a vote's final sum spread over its 16-lane row: after the swap
 // rounds every lane of the vote's row holds Q, and the row is a DPP row, so
 // the self-check and the equation run as rounds of one field operation per
 // lane (ge_is_sane_row, ge_eq_affine_row in hsv_fe16x16.hpp).
-
-__device__ __forceinline__ ge_ext ge_swap_xor(const ge_ext &p, int m) {
-  ge_ext r;
-  HSV_UNROLL
-  for (int i = 0; i < kFeLimbs; ++i) {
-    r.X.v[i] = (uint32_t)__shfl_xor((int)p.X.v[i], m, 64);
-    r.Y.v[i] = (uint32_t)__shfl_xor((int)p.Y.v[i], m, 64);
-    r.Z.v[i] = (uint32_t)__shfl_xor((int)p.Z.v[i], m, 64);
-    r.T.v[i] = (uint32_t)__shfl_xor((int)p.T.v[i], m, 64);
-  }
-  return r;
-}
-
+//
 // The latency form in specialised waves (at <= kCombQuadMax votes): a block
 // takes 64 / L votes.  Wave 0 computes each vote's combined sum
 // Q = [s]B - [k]A over L lanes; the R waves decompress the votes' R at the
@@ -161,11 +150,6 @@ __device__ __forceinline__ ge_ext ge_swap_xor(const ge_ext &p, int m) {
 // votes per wave.  Each vote takes two rows (RowLane2: a product's 16 steps
 // split 8 + 8 between the rows, 25.4 against 32.2 us for the root chain,
 // profiles/r03zz_ubench_lanesplit2.txt), two votes per wave.
-constexpr int kRRows = 2;
-using RLane = RowLane2;
-constexpr int kRVotesPerWave = 4 / kRRows;
-constexpr int kFusedVotes = 64 / kCombLanes;
-constexpr int kFusedRWaves = (kFusedVotes + kRVotesPerWave - 1) / kRVotesPerWave;
 // A hash wave (the last of the block) computes k = H(R || A || M) mod l and
 // its comb digits for the block's votes while the comb wave adds the s half
 // (the B table needs no hash), and hands the digits over in LDS: the comb
@@ -173,9 +157,6 @@ constexpr int kFusedRWaves = (kFusedVotes + kRVotesPerWave - 1) / kRVotesPerWave
 // instead of their sum.  A one-body SHA-512 (half the code fetched cold at
 // each launch) measured no faster: 10.2 against 9.7 us at C1, 13.5 against
 // 13.2 us at C3 (profiles/r04t_qcclk_*.txt).
-constexpr uint32_t kHashWaveIdx = 1 + kFusedRWaves;
-constexpr int kFusedThreads = 64 * (2 + kFusedRWaves);
-
 #ifdef HSV_QC_WAVE_CLOCKS
 // Measurement builds only (tools/qc_wave_clocks.py): lane 0 of every wave
 // stamps the 100 MHz constant clock at fixed points of its path -- 0 entry,
@@ -222,19 +203,6 @@ __device__ uint64_t g_qc_clk[kQcClkWaves][kQcClkSlots];
 // C3 kernel 4.4-4.6 us behind C1 either way, and the barrier ahead of every
 // wave cost C1 3.5 us (profiles/r04i_qc_ab_stage.txt).  The resident service
 // does stage its request in LDS, read in one load by wave 0 (below).
-
-// lane g's 8 P digit bits of a recoded scalar, starting at bit 8 g P
-__device__ __forceinline__ uint64_t lane_digits(const uint32_t r[9], uint32_t g) {
-  constexpr int kBits = 8 * kCombPosPerLane;
-  uint64_t d = 0;
-  HSV_UNROLL
-  for (int q = 0; q < kCombLanes; ++q) {
-    const int w = (q * kBits) / 32, sh = (q * kBits) % 32;
-    const uint64_t v = ((((uint64_t)r[w + 1] << 32) | r[w]) >> sh) & (kBits == 64 ? ~0ull : ((1ull << kBits) - 1));
-    d = g == (uint32_t)q ? v : d;
-  }
-  return d;
-}
 
 // One block's votes [blk * kFusedVotes, ...) of the latency form; the
 // launched kernel below runs it for its blockIdx, the resident service
@@ -706,9 +674,6 @@ extern "C" hipError_t hsv_launch_comb4_build(const uint8_t *encs, uint32_t nkeys
   return hipGetLastError();
 }
 
-// batches up to this many votes take the four-lanes-per-vote form
-static constexpr uint32_t kCombQuadMax = 1u << 12;
-
 #ifdef HSV_QC_WAVE_CLOCKS
 static thread_local uint32_t *t_last_fault = nullptr;  // the calling thread's last latency-form launch
 #endif
@@ -732,7 +697,7 @@ extern "C" hipError_t hsv_launch_comb_verify(const uint32_t *key_idx, const uint
   t_last_fault = done ? fault : nullptr;
 #endif
   const uint32_t inject = (uint32_t)hsvi_inject_mode();
-  if (m <= kCombQuadMax) {  // latency form: four lanes per vote, R decompressed by the R waves
+  if (m <= hsv::kCombQuadMax) {  // latency form: four lanes per vote, R decompressed by the R waves
     hipLaunchKernelGGL(hsv::hsv_comb_verify_quad_fused_kernel, dim3((m + hsv::kFusedVotes - 1) / hsv::kFusedVotes),
                        dim3(hsv::kFusedThreads), 0, stream, key_idx, sig, sig_stride, msg, msg_stride, m, pks, key_flags, nkeys,
                        key_tables, btable, flags_out, inject, fault, done);
@@ -756,7 +721,7 @@ extern "C" uint32_t hsv_comb_resident_votes(void) {
 }
 
 extern "C" uint32_t hsv_comb_marker_blocks(uint32_t m) {
-  return m <= kCombQuadMax ? (m + hsv::kFusedVotes - 1) / hsv::kFusedVotes : 0u;
+  return m <= hsv::kCombQuadMax ? (m + hsv::kFusedVotes - 1) / hsv::kFusedVotes : 0u;
 }
 
 extern "C" uint64_t hsv_comb_table_bytes(void) { return hsv::kCombTableWords * 4ull; }

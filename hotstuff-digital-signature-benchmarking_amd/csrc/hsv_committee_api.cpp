@@ -466,8 +466,62 @@ int committee_msgs_host(const hsv_committee &cm, const uint8_t *pk, const uint8_
                                          cm.dev.n, cm.dev.d_tabptr, cm.dev.digit_bits, c.d_btable, c.d_btable16,
                                          d_flags, nullptr, d_fault, d_totals, st);
       },
-      "allocating the committee message buffers", "hsv_committee_verify_msgs", pk, sig, msgs, offsets, msg_len,
-      msg_stride, n, flags_out);
+      "allocating the committee message buffers", "hsv_committee_verify_msgs", StagedColumn{pk, 32}, sig, msgs, offsets,
+      msg_len, msg_stride, n, flags_out);
+}
+
+// ---- whole messages by member index ------------------------------------------------------
+// hsv_committee_verify_msgs_indexed*: the messages of the calls above, the
+// signer named by its member index as hsv_committee_verify* names it -- no
+// lookup, no miss side, no list lengths to report
+// (hsv_launch_committee_msgs_indexed, hsv_committee_msgs.hip).
+
+// the quad form forced by the test hook needs 8-bit tables
+int indexed_form_ok(const hsv_committee &cm) {
+  if (hsvi_cmsg_indexed_form() == 1 && cm.dev.digit_bits != 8)
+    return fail(HSV_ERR_INVALID_ARG, "the quad form needs a committee with 8-bit tables");
+  return HSV_OK;
+}
+
+// n items already in HBM, in rounds of kChunk in order on `s`
+int committee_msgs_indexed_enqueue(const hsv_committee &cm, const uint32_t *btable, const uint32_t *comb16,
+                                   const uint32_t *d_key_idx, const uint8_t *d_sig, size_t sig_stride,
+                                   const uint8_t *d_msgs, const uint64_t *d_offsets, size_t msg_len, size_t msg_stride,
+                                   size_t n, uint8_t *d_flags, uint32_t *d_fault, hipStream_t s) {
+  for (size_t base = 0; base < n; base += kChunk) {
+    const size_t m = std::min(kChunk, n - base);
+    const hipError_t e = hsv_launch_committee_msgs_indexed(
+        d_key_idx + base, d_sig + base * sig_stride, sig_stride, d_offsets ? d_msgs : d_msgs + base * msg_stride,
+        d_offsets ? d_offsets + base : nullptr, msg_len, msg_stride, (uint32_t)m, cm.dev.d_pks, cm.dev.d_kflags,
+        cm.dev.n, cm.dev.d_tabptr, cm.dev.digit_bits, btable, comb16, d_flags + base, d_fault, s);
+    if (e != hipSuccess) return hip_fail("committee indexed message launch", e);
+  }
+  return HSV_OK;
+}
+
+// The host form: staged_msgs_host with the member indices staged where the
+// other calls stage pk.
+int committee_msgs_indexed_host(const hsv_committee &cm, const uint32_t *key_idx, const uint8_t *sig,
+                                const uint8_t *msgs, const uint64_t *offsets, size_t msg_len, size_t msg_stride,
+                                size_t n, uint8_t *flags_out) {
+  DevCtx &c = ctx(cm.dev.device);
+  return staged_msgs_host(
+      c,
+      [&] {
+        const int rc = ensure_btable(c);
+        return rc == HSV_OK ? ensure_btable16(c) : rc;
+      },
+      nullptr,
+      [&](const uint8_t *d_col, const uint8_t *d_sig, const uint8_t *d_msgs, const uint64_t *d_offsets, size_t m,
+          uint8_t *d_flags, uint32_t *d_fault, hipStream_t st) {
+        return hsv_launch_committee_msgs_indexed(reinterpret_cast<const uint32_t *>(d_col), d_sig, 64, d_msgs, d_offsets,
+                                                 msg_len, msg_stride, (uint32_t)m, cm.dev.d_pks, cm.dev.d_kflags,
+                                                 cm.dev.n, cm.dev.d_tabptr, cm.dev.digit_bits, c.d_btable,
+                                                 c.d_btable16, d_flags, d_fault, st);
+      },
+      "allocating the committee message buffers", "hsv_committee_verify_msgs_indexed",
+      StagedColumn{reinterpret_cast<const uint8_t *>(key_idx), 4}, sig, msgs, offsets, msg_len, msg_stride, n,
+      flags_out);
 }
 
 }  // namespace
@@ -547,5 +601,41 @@ int hsv_committee_verify_msgs_device(const hsv_committee *cm, const uint8_t *d_p
                                 msg_len, msg_stride, n, d_flags, d_strict_bits, call.fault, d_totals, call.stream);
 }
 
-}  // extern "C"
+int hsv_committee_verify_msgs_indexed(hsv_committee *cm, const uint32_t *key_idx, const uint8_t *sig,
+                                      const uint8_t *msgs, const uint64_t *offsets, size_t msg_len, size_t msg_stride,
+                                      size_t m, uint8_t *flags_out) {
+  CallScope call;
+  if (m == 0) return HSV_OK;
+  if (!cm || !key_idx || !sig || !flags_out) return fail(HSV_ERR_INVALID_ARG, "null argument");
+  int rc = msgs_host_args_ok(msgs, offsets, msg_len, msg_stride, m);
+  if (rc != HSV_OK) return rc;
+  rc = ensure_init();  // before the handle is read: without a device there is no committee
+  if (rc != HSV_OK) return rc;
+  rc = indexed_form_ok(*cm);
+  if (rc != HSV_OK) return rc;
+  return committee_msgs_indexed_host(*cm, key_idx, sig, msgs, offsets, msg_len, msg_stride, m, flags_out);
+}
 
+int hsv_committee_verify_msgs_indexed_device(const hsv_committee *cm, const uint32_t *d_key_idx, const uint8_t *d_sig,
+                                             size_t sig_stride, const uint8_t *d_msgs, const uint64_t *d_offsets,
+                                             size_t msg_len, size_t msg_stride, size_t m, uint8_t *d_flags,
+                                             uint32_t *d_fault, void *stream) {
+  if (m == 0) return HSV_OK;
+  if (!cm || !d_key_idx || !d_sig || !d_flags) return fail(HSV_ERR_INVALID_ARG, "null argument");
+  if (m > 0xffffffffu) return fail(HSV_ERR_INVALID_ARG, "batch too large");
+  if (reinterpret_cast<uintptr_t>(d_key_idx) & 3u) return fail(HSV_ERR_ALIGN, "d_key_idx must be 4-byte aligned");
+  // the checks of the pk-addressed call from "null d_msgs" on; there is no pk column to check
+  int rc = msgs_device_args_ok(nullptr, 32, d_sig, sig_stride, d_msgs, d_offsets, msg_len, msg_stride, d_flags, nullptr);
+  if (rc != HSV_OK) return rc;
+  rc = ensure_init();  // before the handle is read: without a device there is no committee
+  if (rc != HSV_OK) return rc;
+  rc = indexed_form_ok(*cm);
+  if (rc != HSV_OK) return rc;
+  DeviceCall call;
+  rc = call.begin(d_sig, stream, d_fault, DeviceCall::kBoth, "committee", cm->dev.device);
+  if (rc != HSV_OK) return rc;
+  return committee_msgs_indexed_enqueue(*cm, call.comb, call.comb16, d_key_idx, d_sig, sig_stride, d_msgs, d_offsets,
+                                        msg_len, msg_stride, m, d_flags, call.fault, call.stream);
+}
+
+}  // extern "C"

@@ -396,17 +396,24 @@ int tx_device_args_ok(const uint64_t *d_offsets, size_t tx_size, const uint8_t *
                       const uint32_t *d_strict_bits);
 
 // n whole messages through a slot of device c and one StagedBlock per launch
-// (flags | pk | sig | offsets rebased to the chunk | message bytes): at most
-// kChunk items and g_stage_bytes message bytes per launch.  `tables` ensures
-// the B tables `launch` reads (current device c.device); alloc_what and
-// finish_where are the caller's texts for hsv_last_error.
-using MsgsLaunch = std::function<hipError_t(const uint8_t *d_pk, const uint8_t *d_sig, const uint8_t *d_msgs,
+// (flags | column | sig | offsets rebased to the chunk | message bytes): at
+// most kChunk items and g_stage_bytes message bytes per launch.  The column
+// says who signed each item: the 32 pk bytes of the pk-addressed calls, or the
+// 4-byte member index of hsv_committee_verify_msgs_indexed; `launch` gets its
+// device copy as d_col.  `tables` ensures the B tables `launch` reads (current
+// device c.device); alloc_what and finish_where are the caller's texts for
+// hsv_last_error.
+struct StagedColumn {
+  const uint8_t *src;
+  size_t item_bytes;  // 32 (pk) or 4 (member index)
+};
+using MsgsLaunch = std::function<hipError_t(const uint8_t *d_col, const uint8_t *d_sig, const uint8_t *d_msgs,
                                             const uint64_t *d_offsets, size_t m, uint8_t *d_flags, uint32_t *d_fault,
                                             hipStream_t stream)>;
 int staged_msgs_host(DevCtx &c, const std::function<int()> &tables, const StagedBegin &begin,
-                     const MsgsLaunch &launch, const char *alloc_what, const char *finish_where, const uint8_t *pk,
-                     const uint8_t *sig, const uint8_t *msgs, const uint64_t *offsets, size_t msg_len,
-                     size_t msg_stride, size_t n, uint8_t *flags_out);
+                     const MsgsLaunch &launch, const char *alloc_what, const char *finish_where,
+                     const StagedColumn &col, const uint8_t *sig, const uint8_t *msgs, const uint64_t *offsets,
+                     size_t msg_len, size_t msg_stride, size_t n, uint8_t *flags_out);
 // the checks of the two *_verify_msgs host calls after their null test ...
 int msgs_host_args_ok(const uint8_t *msgs, const uint64_t *offsets, size_t msg_len, size_t msg_stride, size_t n);
 // ... and of the two device calls from "null d_msgs" on

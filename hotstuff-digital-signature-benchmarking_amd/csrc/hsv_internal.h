@@ -304,6 +304,30 @@ hipError_t hsv_launch_committee_msgs(const uint8_t *pk, uint64_t pk_stride, cons
                                      const uint32_t *const *key_tables, int digit_bits, const uint32_t *btable,
                                      const uint32_t *comb16, uint8_t *flags_out, uint32_t *strict_bits,
                                      uint32_t *fault, uint64_t *totals, hipStream_t stream);
+// One round (n <= 2^22) of hsv_committee_verify_msgs_indexed* (hsv_committee_msgs.hip):
+// the messages of hsv_launch_verify_msgs, item i signed by member key_idx[i] (an
+// index >= nkeys: flags 0, as a decreasing pair of offsets).  At n <= 2^12 with
+// 8-bit tables one launch of the latency form (hsv_cmsg_quad_kernel), else a
+// memset of the counters and two launches (hsv_cmsg_index_kernel and the comb
+// pass of hsv_launch_committee_msgs).  Every flag byte is written; no strict
+// words; fault as hsv_launch_comb_verify; btable / comb16: the narrow and the
+// wide comb of B.
+hipError_t hsv_launch_committee_msgs_indexed(const uint32_t *key_idx, const uint8_t *sig, uint64_t sig_stride,
+                                             const uint8_t *msgs, const uint64_t *offsets, uint64_t msg_len,
+                                             uint64_t msg_stride, uint32_t n, const uint8_t *pks,
+                                             const uint8_t *key_flags, uint32_t nkeys,
+                                             const uint32_t *const *key_tables, int digit_bits, const uint32_t *btable,
+                                             const uint32_t *comb16, uint8_t *flags_out, uint32_t *fault,
+                                             hipStream_t stream);
+// Its route (hsv_test_cmsg_indexed_form): -1 by n and the table width
+// (default), 0 the two launches at every n, 1 the latency form at every n (8-bit
+// tables only).  Returns the previous mode, or -2 for an unknown one.
+// hsvi_cmsg_indexed_counts: {latency-form launches, two-launch rounds} of the
+// process so far and the items those rounds put on their hit lists on the
+// current device (valid once the caller's streams are synchronised).
+int hsvi_set_cmsg_indexed_form(int mode);
+int hsvi_cmsg_indexed_form(void);
+int hsvi_cmsg_indexed_counts(uint64_t out[3]);
 // flags 0 (and STRICT_OK bit cleared) for transactions shorter than 96 bytes
 hipError_t hsv_launch_tx_mask(const uint64_t *offsets, uint32_t n, uint8_t *flags, uint32_t *strict_bits,
                               hipStream_t stream);

@@ -66,9 +66,9 @@ int msgs_device_args_ok(const uint8_t *d_pk, size_t pk_stride, const uint8_t *d_
 
 // The one walk of the staged message host forms (hsv_host.h).
 int staged_msgs_host(DevCtx &c, const std::function<int()> &tables, const StagedBegin &begin,
-                     const MsgsLaunch &launch, const char *alloc_what, const char *finish_where, const uint8_t *pk,
-                     const uint8_t *sig, const uint8_t *msgs, const uint64_t *offsets, size_t msg_len,
-                     size_t msg_stride, size_t n, uint8_t *flags_out) {
+                     const MsgsLaunch &launch, const char *alloc_what, const char *finish_where,
+                     const StagedColumn &col, const uint8_t *sig, const uint8_t *msgs, const uint64_t *offsets,
+                     size_t msg_len, size_t msg_stride, size_t n, uint8_t *flags_out) {
   DeviceGuard guard(c.device);
   if (guard.status() != hipSuccess) return hip_fail("hipSetDevice", guard.status());
   int rc = tables();
@@ -86,12 +86,12 @@ int staged_msgs_host(DevCtx &c, const std::function<int()> &tables, const Staged
     b = span.chunk_end(a, n, kChunk, g_stage_bytes.load());
     const size_t m = b - a, bytes = span.span_bytes(a, b);
     StagedBlock blk(st);
-    const size_t off_flags = blk.add(m), off_pk = blk.add(m * 32), off_sig = blk.add(m * 64);
+    const size_t off_flags = blk.add(m), off_col = blk.add(m * col.item_bytes), off_sig = blk.add(m * 64);
     const size_t off_offs = blk.add(offsets ? (m + 1) * 8 : 0), off_msg = blk.add(bytes);
     // unwritten flags read as rejections
     rc = blk.alloc(alloc_what, m);
     if (rc != HSV_OK) return rc;
-    blk.in(off_pk, pk + a * 32, m * 32);
+    blk.in(off_col, col.src + a * col.item_bytes, m * col.item_bytes);
     blk.in(off_sig, sig + a * 64, m * 64);
     if (offsets) {
       rel.resize(m + 1);
@@ -100,7 +100,7 @@ int staged_msgs_host(DevCtx &c, const std::function<int()> &tables, const Staged
     }
     blk.in(off_msg, msgs + span.first_byte(a), bytes);
     if (blk.ok())
-      blk.step(launch(blk.at(off_pk), blk.at(off_sig), blk.at(off_msg),
+      blk.step(launch(blk.at(off_col), blk.at(off_sig), blk.at(off_msg),
                       offsets ? reinterpret_cast<uint64_t *>(blk.at(off_offs)) : nullptr, m, blk.at(off_flags),
                       blk.fault(), st));
     blk.out(flags_out + a, off_flags, m);
@@ -147,8 +147,8 @@ int hsv_verify_msgs(const uint8_t *pk, const uint8_t *sig, const uint8_t *msgs, 
         return hsv_launch_verify_msgs(d_pk, 32, d_sig, 64, d_msgs, d_offsets, msg_len, msg_stride, (uint32_t)m,
                                       d_flags, nullptr, c.d_btable16, d_fault, st);
       },
-      "allocating the message verification buffers", "hsv_verify_msgs", pk, sig, msgs, offsets, msg_len, msg_stride,
-      n, flags_out);
+      "allocating the message verification buffers", "hsv_verify_msgs", StagedColumn{pk, 32}, sig, msgs, offsets,
+      msg_len, msg_stride, n, flags_out);
 }
 
 }  // extern "C"

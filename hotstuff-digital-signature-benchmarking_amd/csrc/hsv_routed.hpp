@@ -106,6 +106,13 @@ struct RoutedRound {
     canary_bytes = up256((size_t)grid_g * kBlock * sizeof(uint32_t));
     return hipSuccess;
   }
+  // a round without a generic pass (items addressed by member index have no
+  // miss side): no per-lane tables and no canaries, the workspace starts at the
+  // counters
+  void comb_only() {
+    grid_g = 0;
+    vt_bytes = canary_bytes = 0;
+  }
   size_t head_bytes() const { return vt_bytes + 256 + canary_bytes; }
   // the counters and the strict words zeroed on the stream, before the route launch
   static hipError_t zero(RoutedCounters *ctr, uint32_t *strict_bits, uint32_t n, hipStream_t stream) {

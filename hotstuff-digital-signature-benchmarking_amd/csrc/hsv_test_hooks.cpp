@@ -84,6 +84,11 @@ int hsv_test_committee_tx_counts(uint64_t out[3]) { return hsvh::committee_tx_co
 int hsv_test_committee_msgs_counts(uint64_t out[3]) { return hsvh::committee_msgs_counts(out); }
 int hsv_test_msgs_small(int mode) { return hsvi_set_msgs_small(mode); }
 int hsv_test_msgs_form_counts(uint64_t out[5]) { return hsvi_msgs_form_counts(out); }
+int hsv_test_cmsg_indexed_form(int mode) { return hsvi_set_cmsg_indexed_form(mode); }
+int hsv_test_cmsg_indexed_counts(uint64_t out[3]) {
+  if (!out) return HSV_ERR_INVALID_ARG;
+  return hsvi_cmsg_indexed_counts(out) == 0 ? HSV_OK : HSV_ERR_HIP;
+}
 size_t hsv_test_stage_bytes(size_t bytes) { return hsvh::g_stage_bytes.exchange(bytes ? bytes : hsvh::kStageBytes); }
 
 }  // extern "C"

@@ -125,6 +125,19 @@ HSV_API int hsv_test_msgs_small(int mode);
 /* Launches of hsv_verify_msgs* in this process so far, by form: out[0]
  * two-launch, out[1] quad, out[2] joint, out[3] row, out[4] pair.  HSV_OK. */
 HSV_API int hsv_test_msgs_form_counts(uint64_t out[5]);
+/* Tests and measurement (tools/committee_msgs_indexed_bench.py): how
+ * hsv_committee_verify_msgs_indexed* verifies a round.  -1 = by its size and the
+ * committee's table width, the product's rule (the default); 0 = the two
+ * launches of the bulk route at every size; 1 = the one-launch latency form at
+ * every size -- a call on a compact committee then answers
+ * HSV_ERR_INVALID_ARG.  Process-wide; the product library has no such switch.
+ * Returns the previous mode, or -2 for an unknown one.  Needs no device. */
+HSV_API int hsv_test_cmsg_indexed_form(int mode);
+/* What those calls launched in this process so far: out[0] latency-form
+ * launches, out[1] rounds of the bulk route, out[2] the items those rounds put
+ * on their hit lists (counted on the current device: valid once the caller has
+ * synchronised its streams).  HSV_OK, or HSV_ERR_HIP. */
+HSV_API int hsv_test_cmsg_indexed_counts(uint64_t out[3]);
 
 #ifdef __cplusplus
 }

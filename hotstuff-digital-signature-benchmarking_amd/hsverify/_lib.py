@@ -31,7 +31,7 @@ HOOKS = ("hsv_test_inject_fault", "hsv_test_inject_mode", "hsv_test_corrupt_auto
          "hsv_test_pipe_schedule", "hsv_test_numa_plan", "hsv_test_pinned_thread_cpus", "hsv_test_signer_group",
          "hsv_test_tx_sign_chunk", "hsv_test_msg_sign_chunk", "hsv_test_stage_bytes", "hsv_test_committee_tx_counts",
          "hsv_test_committee_msgs_counts", "hsv_test_msgs_small", "hsv_test_msgs_form_counts",
-         "hsv_test_field_ops", "hsv_test_scalar_ops")
+         "hsv_test_field_ops", "hsv_test_scalar_ops", "hsv_test_cmsg_indexed_form", "hsv_test_cmsg_indexed_counts")
 
 # flag bits (include/hsv.h)
 STRICT_OK = 0x01
@@ -133,6 +133,12 @@ def _declare(lib):
         "hsv_committee_verify_msgs_device": (ctypes.c_int, [ctypes.c_void_p, c_u8p, sz, c_u8p, sz, c_u8p, c_u8p, sz, sz,
                                                             sz, c_u8p, c_u8p, ctypes.c_void_p, ctypes.c_void_p]),
         "hsv_test_committee_msgs_counts": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64)]),
+        "hsv_committee_verify_msgs_indexed": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u8p, c_u8p, c_u8p, sz, sz, sz,
+                                                             c_u8p]),
+        "hsv_committee_verify_msgs_indexed_device": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u8p, sz, c_u8p, c_u8p, sz,
+                                                                    sz, sz, c_u8p, ctypes.c_void_p, ctypes.c_void_p]),
+        "hsv_test_cmsg_indexed_form": (ctypes.c_int, [ctypes.c_int]),
+        "hsv_test_cmsg_indexed_counts": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64)]),
         "hsv_set_variant": (ctypes.c_int, [ctypes.c_int]),
         "hsv_get_variant": (ctypes.c_int, []),
         "hsv_set_lattice_bits": (ctypes.c_int, [ctypes.c_int]),
@@ -176,7 +182,8 @@ def _declare(lib):
                              "hsv_signer_sign_transactions", "hsv_signer_sign_transactions_device",
                              "hsv_signer_sign_msgs", "hsv_signer_sign_msgs_device",
                              "hsv_committee_verify_transactions", "hsv_committee_verify_transactions_device",
-                             "hsv_committee_verify_msgs", "hsv_committee_verify_msgs_device"}
+                             "hsv_committee_verify_msgs", "hsv_committee_verify_msgs_device",
+                             "hsv_committee_verify_msgs_indexed", "hsv_committee_verify_msgs_indexed_device"}
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None) if name in optional else getattr(lib, name)
         if fn is None:

@@ -156,3 +156,22 @@ def committee_msgs_counts() -> tuple:
     out = (ctypes.c_uint64 * 3)()
     _lib.check(_lib.hook("hsv_test_committee_msgs_counts")(out), "hsv_test_committee_msgs_counts")
     return int(out[0]), int(out[1]), int(out[2])
+
+
+def cmsg_indexed_form(mode: int) -> int:
+    """Route of Committee.verify_msgs_indexed* (hsv_test_cmsg_indexed_form): -1
+    by size and table width (the product's rule), 0 the bulk route, 1 the
+    one-launch latency form at every size.  Returns the previous mode."""
+    prev = int(_lib.hook("hsv_test_cmsg_indexed_form")(int(mode)))
+    if prev == -2:
+        raise ValueError(f"unknown mode {mode}")
+    return prev
+
+
+def cmsg_indexed_counts() -> tuple:
+    """(latency-form launches, bulk rounds, items on the bulk hit lists) of
+    Committee.verify_msgs_indexed* in this process so far (test library; after
+    the device form, synchronise first)."""
+    out = (ctypes.c_uint64 * 3)()
+    _lib.check(_lib.hook("hsv_test_cmsg_indexed_counts")(out), "hsv_test_cmsg_indexed_counts")
+    return int(out[0]), int(out[1]), int(out[2])

@@ -189,6 +189,58 @@ class Committee:
             p(flags), p(strict_bits), _fault_ptr(fault), ctypes.c_void_p(stream))
         _lib.check(rc, "hsv_committee_verify_msgs_device")
 
+    def verify_msgs_indexed(self, key_idx, sig, msgs) -> np.ndarray:
+        """Whole messages by member index: key_idx (m,) member indices
+        (``index`` per vote), sig (m,64), ``msgs`` a sequence of m ``bytes`` or
+        a ``(buffer, offsets)`` pair -> flag bytes, bit for bit those of
+        verifier.verify_msgs for (member's key, sig, message); an index >=
+        len(self) gives flags 0.  Decreasing offsets raise HsvLibraryError."""
+        from .verifier import pack_msgs
+        idx = np.ascontiguousarray(key_idx, np.uint32).reshape(-1)
+        sig = np.ascontiguousarray(sig, dtype=np.uint8).reshape(-1, 64)
+        m = idx.size
+        if sig.shape[0] != m:
+            raise ValueError("key_idx/sig length mismatch")
+        if isinstance(msgs, tuple) and len(msgs) == 2 and not isinstance(msgs[0], (bytes, bytearray, memoryview)):
+            buf = np.ascontiguousarray(msgs[0], dtype=np.uint8).reshape(-1)
+            offsets = np.ascontiguousarray(msgs[1], dtype=np.uint64).reshape(-1)
+        else:
+            buf, offsets = pack_msgs(msgs)
+        if offsets.size != m + 1:
+            raise ValueError("one message per item (m + 1 offsets)")
+        if m and buf.size < int(offsets.max()):
+            raise ValueError("offsets run past the buffer")
+        out = np.zeros(m, dtype=np.uint8)
+        if m:
+            _lib.check(self._lib.hsv_committee_verify_msgs_indexed(
+                self._h, _ptr(idx), _ptr(sig), _ptr(buf) if buf.size else None, _ptr(offsets), 0, 0, m, _ptr(out)),
+                "hsv_committee_verify_msgs_indexed")
+        return out
+
+    def verify_msgs_indexed_device(self, key_idx, sig, msgs, offsets=None, msg_len: int = 0,
+                                   msg_stride: int | None = None, flags=None, stream=None, fault=None) -> None:
+        """Device tensors, shaped as verify_msgs_device with key_idx (m,) int32
+        in the place of pk: sig (m,64) rows at a stride that is a multiple of
+        16, ``msgs`` at any alignment, ``offsets`` int64 (m + 1) or None for
+        ``msg_len`` bytes per item at ``msg_stride`` (default msg_len; 0 = one
+        shared message); ``flags`` (m,) uint8, required (there are no strict
+        bits).  One launch at m <= 4096 on full tables.  No synchronisation."""
+        from .verifier import _fault_ptr
+        import torch
+        m = key_idx.shape[0]
+        for t in (sig, msgs, offsets, flags, fault):
+            if t is not None and t.device != key_idx.device:
+                raise ValueError(f"all tensors must live on {key_idx.device}, got {t.device}")
+        if msg_stride is None:
+            msg_stride = msg_len
+        if stream is None:
+            stream = torch.cuda.current_stream(key_idx.device).cuda_stream
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        rc = self._lib.hsv_committee_verify_msgs_indexed_device(
+            self._h, p(key_idx), p(sig), sig.stride(0), p(msgs), p(offsets), msg_len, msg_stride, m, p(flags),
+            _fault_ptr(fault), ctypes.c_void_p(stream))
+        _lib.check(rc, "hsv_committee_verify_msgs_indexed_device")
+
     def close(self) -> None:
         if self._h:
             self._lib.hsv_committee_destroy(self._h)

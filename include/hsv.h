@@ -10,7 +10,8 @@
  *   (batched strict API)                     -> hsv_verify
  *   (the same over whole messages of any length, RFC 8032 5.1.7) -> hsv_verify_msgs,
  *                                                                   hsv_verify_msgs_device,
- *                                                                   hsv_committee_verify_msgs*
+ *                                                                   hsv_committee_verify_msgs*,
+ *                                                                   hsv_committee_verify_msgs_indexed*
  *   crypto::Signature::new           crypto/src/lib.rs:185-191  -> hsv_sign, hsv_signer_sign*
  *   crypto::generate_keypair         crypto/src/lib.rs:167-175  -> hsv_public_key, hsv_signer_create
  *   mempool transaction check  mempool/src/batch_maker.rs:79-85 -> hsv_verify_transactions*,
@@ -109,7 +110,7 @@ HSV_API const char *hsv_last_error(void);
  * hsv_verify_transactions_device) take the optional d_fault argument before
  * `stream`; a caller built against 0.2.x headers must be rebuilt (check
  * HSV_ABI_VERSION against hsv_abi_version() at startup).  Entry points added
- * since (the last: hsv_committee_create_ex) change no existing signature
+ * since (the last: hsv_committee_verify_msgs_indexed*) change no existing signature
  * and leave both the version and HSV_ABI_VERSION as they are. */
 #define HSV_ABI_VERSION 3
 HSV_API const char *hsv_version(void);
@@ -388,6 +389,51 @@ HSV_API int hsv_committee_verify_msgs_device(const hsv_committee *c, const uint8
                                              const uint64_t *d_offsets, size_t msg_len, size_t msg_stride,
                                              size_t n, uint8_t *d_flags, uint32_t *d_strict_bits,
                                              uint32_t *d_fault, void *stream);
+/* The same whole messages with each signer named by its member index, as
+ * hsv_committee_verify* names it (hsv_committee_index per vote, on the host):
+ * a QC or TC whose votes sign whole messages.  Flags are bit for bit those of
+ * hsv_verify_msgs* for (member key_idx[i]'s 32 key bytes, sig i, message i);
+ * an index >= hsv_committee_size gives flags 0, as hsv_committee_verify does;
+ * of a key listed twice either index gives the same flags.  Message
+ * addressing as hsv_committee_verify_msgs* above (offsets / msg_len and
+ * msg_stride, empty messages, msgs at any alignment).
+ * Host form: synchronous, on the committee's device, staged and chunked as
+ * hsv_committee_verify_msgs with the indices in the place of pk; decreasing
+ * offsets are HSV_ERR_INVALID_ARG before any device work; a failed device
+ * self-check is HSV_ERR_DEVICE_FAULT; without a GPU, HSV_ERR_NO_DEVICE.  It
+ * uses neither the resident service nor the zero-copy markers nor the
+ * automatic cache.
+ * Device form: stream-ordered, never synchronises; device = the committee's
+ * (as hsv_committee_verify_device).  d_sig and sig_stride are multiples of 16
+ * (HSV_ERR_ALIGN), d_offsets 8-byte and d_key_idx 4-byte aligned.  d_flags is
+ * required and every one of its m bytes is written; there are no strict bits
+ * (hsv_committee_verify_device has none either).  An item whose offsets
+ * decrease gets flags 0 and leaves its neighbours alone.  d_fault as
+ * hsv_committee_verify_device.  At m <= 2^12 on a committee with 8-bit tables
+ * the call is ONE launch without a memset (the 16-lanes-per-vote latency form
+ * of hsv_committee_verify_device with a hash wave that reads whole messages);
+ * above, and at every m on a compact committee, a memset and two launches
+ * per round of 2^22 items.
+ * When to use it: when the caller knows the member index of every signer --
+ * there is no route for strangers here; mixed batches belong to
+ * hsv_committee_verify_msgs*.  Measured (profiles/committee_msgs_indexed_bench.json,
+ * K = 1000 keys, device-resident items, p50 of the call plus a
+ * stream synchronise, against hsv_committee_verify_msgs_device and
+ * hsv_verify_msgs_device on the same bytes in the same run): 0.052 ms at 67
+ * votes of 32 bytes (0.273 and 0.116 ms), 0.078 ms at 416 bytes (0.291 and
+ * 0.146), 0.069 - 0.120 ms at 667 votes (0.289 - 0.371 and 0.131 - 0.214),
+ * 0.130 - 0.262 ms at 4096 (0.300 - 0.394 and 0.485 - 0.539); on 32-byte
+ * messages 0.90 - 1.01 x hsv_committee_verify_device on the same votes as
+ * digests.  From about 100 bytes on, the hash of the block's longest message
+ * decides a small call's time.  At 2^20 items 0.98 - 1.00 x the pk-addressed
+ * call's time. */
+HSV_API int hsv_committee_verify_msgs_indexed(hsv_committee *c, const uint32_t *key_idx, const uint8_t *sig,
+                                              const uint8_t *msgs, const uint64_t *offsets, size_t msg_len,
+                                              size_t msg_stride, size_t m, uint8_t *flags_out);
+HSV_API int hsv_committee_verify_msgs_indexed_device(const hsv_committee *c, const uint32_t *d_key_idx,
+                                                     const uint8_t *d_sig, size_t sig_stride, const uint8_t *d_msgs,
+                                                     const uint64_t *d_offsets, size_t msg_len, size_t msg_stride,
+                                                     size_t m, uint8_t *d_flags, uint32_t *d_fault, void *stream);
 
 /* ---- mempool transactions -------------------------- */
 /* A client transaction is  message || pk (32 B) || sig (64 B, R||s)  and its

@@ -493,6 +493,66 @@ class Signer {
   hsv_signer *h_ = nullptr;
 };
 
+// A committee's keys with their comb tables on the GPU (hsv_committee_*,
+// hsv.h), for a QC or TC whose votes sign whole messages: the caller looks each
+// vote's author up once (index) and verifies the votes by member index, the
+// committee form of crypto::Signature::verify_msgs.  Owns the handle; errors
+// throw crypto::InfrastructureError (there is no CPU fallback).
+class Committee {
+ public:
+  explicit Committee(const std::vector<crypto::PublicKey> &keys, bool compact = false) {
+    std::vector<uint8_t> raw(keys.size() * 32);
+    for (size_t i = 0; i < keys.size(); ++i) std::memcpy(raw.data() + 32 * i, keys[i].bytes.data(), 32);
+    crypto::check_infra(hsv_committee_create_ex(raw.data(), keys.size(),
+                                                compact ? HSV_COMMITTEE_DIGITS_COMPACT : HSV_COMMITTEE_DIGITS_FULL,
+                                                &h_),
+                        "hsv_committee_create_ex");
+  }
+  ~Committee() { hsv_committee_destroy(h_); }
+  Committee(const Committee &) = delete;
+  Committee &operator=(const Committee &) = delete;
+
+  size_t size() const { return hsv_committee_size(h_); }
+  // the member index of pk, or -1 for a stranger
+  int64_t index(const crypto::PublicKey &pk) const { return hsv_committee_index(h_, pk.bytes.data()); }
+  // Votes over whole messages by member index (hsv_committee_verify_msgs_indexed):
+  // item i is sigs[i] over msgs[i] under member key_idx[i].  Returns the
+  // per-item HSV_* flag bytes, those of Signature::verify_msgs for the member's
+  // key; an index >= size() gives flags 0.
+  std::vector<uint8_t> verify_msgs_indexed(const std::vector<uint32_t> &key_idx,
+                                           const std::vector<crypto::Signature> &sigs,
+                                           const std::vector<std::vector<uint8_t>> &msgs) {
+    const size_t m = key_idx.size();
+    if (sigs.size() != m || msgs.size() != m)
+      throw std::invalid_argument("verify_msgs_indexed: one signature and one message per index");
+    std::vector<uint8_t> sig(m * 64), buf, flags(m);
+    std::vector<uint64_t> offsets(m + 1, 0);
+    for (size_t i = 0; i < m; ++i) {
+      std::memcpy(sig.data() + 64 * i, sigs[i].part1.data(), 32);
+      std::memcpy(sig.data() + 64 * i + 32, sigs[i].part2.data(), 32);
+      buf.insert(buf.end(), msgs[i].begin(), msgs[i].end());
+      offsets[i + 1] = buf.size();
+    }
+    crypto::check_infra(hsv_committee_verify_msgs_indexed(h_, key_idx.data(), sig.data(), buf.data(), offsets.data(), 0,
+                                                          0, m, flags.data()),
+                        "hsv_committee_verify_msgs_indexed");
+    return flags;
+  }
+  // device-resident, stream-ordered form (hsv_committee_verify_msgs_indexed_device)
+  void verify_msgs_indexed_device(const uint32_t *d_key_idx, const uint8_t *d_sig, size_t sig_stride,
+                                  const uint8_t *d_msgs, const uint64_t *d_offsets, size_t msg_len, size_t msg_stride,
+                                  size_t m, uint8_t *d_flags, uint32_t *d_fault = nullptr,
+                                  void *stream = nullptr) const {
+    crypto::check_infra(hsv_committee_verify_msgs_indexed_device(h_, d_key_idx, d_sig, sig_stride, d_msgs, d_offsets,
+                                                                 msg_len, msg_stride, m, d_flags, d_fault, stream),
+                        "hsv_committee_verify_msgs_indexed_device");
+  }
+  hsv_committee *handle() const { return h_; }
+
+ private:
+  hsv_committee *h_ = nullptr;
+};
+
 }  // namespace hsv
 
 #endif  // HSV_CRYPTO_HPP_
