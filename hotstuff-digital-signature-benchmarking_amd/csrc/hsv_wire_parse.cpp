@@ -1,4 +1,5 @@
-// Bincode parsers of QC / TC certificates (see hsv_wire_parse.h).
+// Bincode parsers of QC / TC certificates, blocks, votes and timeouts (see
+// hsv_wire_parse.h).
 //
 // Layouts (bincode 1.3 default options: little-endian, fixed-width integers,
 // u64 length prefixes; the serde derives of the reference):
@@ -7,6 +8,12 @@
 //   Signature         part1 (32) || part2 (32) crypto/src/lib.rs:176-182
 //   QC  = hash: Digest | round: u64 | votes: Vec<(PublicKey, Signature)>
 //   TC  = round: u64 | votes: Vec<(PublicKey, Signature, Round)>
+//   Block   = qc: QC | tc: Option<TC> (u8 tag 0 / 1) | author: PublicKey |
+//             round: u64 | payload: Vec<Digest> | signature
+//   Vote    = hash: Digest | round: u64 | author: PublicKey | signature
+//   Timeout = high_qc: QC | round: u64 | author: PublicKey | signature
+// An embedded certificate ends where its votes end; only the outermost object
+// checks for trailing bytes.
 // PublicKey::decode_base64 (crypto/src/lib.rs:73-79) runs base64 0.13's
 // standard decoder and keeps the first 32 bytes; shorter decodings are an
 // error.  This decoder follows the same rules: standard alphabet, optional
@@ -22,7 +29,7 @@
 #include <immintrin.h>
 #endif
 
-#include "hsv_sha512.hpp"
+#include "hsv_proposal.hpp"
 
 namespace hsvw {
 namespace {
@@ -155,8 +162,73 @@ bool read_public_key(Reader &r, uint8_t pk[32]) {
   return b64_decode_prefix(s, (size_t)len, pk, 32) >= 32;
 }
 
-void put_le64(uint8_t *p, uint64_t v) {
-  for (int b = 0; b < 8; ++b) p[b] = (uint8_t)(v >> (8 * b));
+// The votes of a QC (kRound false) or a TC (true): a u64 count, bounded by the
+// bytes left before anything is allocated, then per vote PublicKey str | R || s
+// (| high_qc_round u64).  room(n) sizes the output once, slot(i, pk, sig) names
+// where vote i's 32 key bytes and 64 signature bytes go, round(i, r) takes its
+// high_qc_round.  No trailing-byte check: the certificate may be embedded.
+template <bool kRound, class Room, class Slot, class Round>
+bool read_votes(Reader &r, size_t &n, std::string &err, Room room, Slot slot, Round round) {
+  uint64_t nv = 0;
+  if (!r.u64(nv)) {
+    err = "truncated vote count";
+    return false;
+  }
+  if (nv > r.left / (kRound ? 80 : 72)) {  // a vote is at least 8 + 0 + 64 (+ 8) bytes
+    err = "vote count exceeds the buffer";
+    return false;
+  }
+  n = (size_t)nv;
+  room(n);
+  for (size_t i = 0; i < n; ++i) {
+    uint8_t *pk = nullptr, *dst = nullptr;
+    slot(i, pk, dst);
+    const uint8_t *sig = nullptr;
+    uint64_t hqc = 0;
+    if (!read_public_key(r, pk)) {
+      err = "vote " + std::to_string(i) + ": bad public key";
+      return false;
+    }
+    if (!r.bytes(sig, 64) || (kRound && !r.u64(hqc))) {
+      err = "vote " + std::to_string(i) + ": truncated";
+      return false;
+    }
+    std::memcpy(dst, sig, 64);
+    if (kRound) round(i, hqc);
+  }
+  return true;
+}
+
+// QC = hash | round | votes, as n packed 96-byte records pk || R || s
+bool read_qc(Reader &r, uint8_t hash[32], uint64_t &round, std::vector<uint8_t> &votes, size_t &n, std::string &err) {
+  const uint8_t *h = nullptr;
+  if (!r.bytes(h, 32) || !r.u64(round)) {
+    err = "truncated QC header";
+    return false;
+  }
+  std::memcpy(hash, h, 32);
+  return read_votes<false>(
+      r, n, err, [&](size_t k) { votes.resize(k * 96); },  // every byte is written
+      [&](size_t i, uint8_t *&pk, uint8_t *&sig) {
+        pk = votes.data() + i * 96;
+        sig = pk + 32;
+      },
+      [](size_t, uint64_t) {});
+}
+
+// TC = round | votes, as n 104-byte records pk || R || s || high_qc_round_le
+bool read_tc(Reader &r, uint64_t &round, std::vector<uint8_t> &votes, size_t &n, std::string &err) {
+  if (!r.u64(round)) {
+    err = "truncated TC header";
+    return false;
+  }
+  return read_votes<true>(
+      r, n, err, [&](size_t k) { votes.resize(k * 104); },
+      [&](size_t i, uint8_t *&pk, uint8_t *&sig) {
+        pk = votes.data() + i * 104;
+        sig = pk + 32;
+      },
+      [&](size_t i, uint64_t hqc) { hsvp::put_le64(votes.data() + i * 104 + 96, hqc); });
 }
 
 }  // namespace
@@ -178,40 +250,13 @@ bool parse_qc(const uint8_t *buf, size_t len, QcParsed &out, std::string &err) {
     return false;
   }
   Reader r{buf, len};
-  const uint8_t *hash = nullptr;
-  uint64_t nv = 0;
-  if (!r.bytes(hash, 32) || !r.u64(out.round) || !r.u64(nv)) {
-    err = "truncated QC header";
-    return false;
-  }
-  if (nv > r.left / 72) {  // a vote is at least 8 + 0 + 64 bytes
-    err = "vote count exceeds the buffer";
-    return false;
-  }
-  out.n = (size_t)nv;
-  out.votes.resize(out.n * 96);  // every byte is written below
-  for (size_t i = 0; i < out.n; ++i) {
-    uint8_t *v = out.votes.data() + i * 96;
-    const uint8_t *sig = nullptr;
-    if (!read_public_key(r, v)) {
-      err = "vote " + std::to_string(i) + ": bad public key";
-      return false;
-    }
-    if (!r.bytes(sig, 64)) {
-      err = "vote " + std::to_string(i) + ": truncated signature";
-      return false;
-    }
-    std::memcpy(v + 32, sig, 64);
-  }
+  uint8_t hash[32];
+  if (!read_qc(r, hash, out.round, out.votes, out.n, err)) return false;
   if (r.left != 0) {
     err = "trailing bytes after the QC";
     return false;
   }
-  uint8_t pre[40], h[64];
-  std::memcpy(pre, hash, 32);
-  put_le64(pre + 32, out.round);
-  hsv::sha512_bytes(pre, sizeof(pre), h);
-  std::memcpy(out.digest, h, 32);
+  hsvp::qc_digest(hash, out.round, out.digest);
   return true;
 }
 
@@ -221,67 +266,138 @@ bool parse_tc(const uint8_t *buf, size_t len, TcParsed &out, std::string &err) {
     return false;
   }
   Reader r{buf, len};
-  uint64_t nv = 0;
-  if (!r.u64(out.round) || !r.u64(nv)) {
+  if (!r.u64(out.round)) {
     err = "truncated TC header";
     return false;
   }
-  if (nv > r.left / 80) {  // 8 + 0 + 64 + 8 bytes at least
-    err = "vote count exceeds the buffer";
-    return false;
-  }
-  out.n = (size_t)nv;
-  out.pks.resize(out.n * 32);  // every byte is written below
-  out.sigs.resize(out.n * 64);
-  out.digests.resize(out.n * 32);
-  // the per-vote digest depends only on (round, high_qc_round), and a TC's
-  // high_qc_rounds take few distinct values (the last rounds before a
-  // timeout): hash each once.  A small array searched from the last hit, not
-  // a hash map -- no allocation per call, and a C3 TC's 667 lookups cost a
-  // few compares each (the map made the parse ~28 us of a 0.092 ms bincode
-  // TC on the GPU box, profiles/r05e_bench_detail.json).
-  constexpr size_t kMemo = 32;
-  uint64_t memo_key[kMemo];
-  uint8_t memo_dig[kMemo][32];
-  size_t memo_n = 0, memo_last = 0;
-  for (size_t i = 0; i < out.n; ++i) {
-    const uint8_t *sig = nullptr;
-    uint64_t hqc = 0;
-    if (!read_public_key(r, out.pks.data() + i * 32)) {
-      err = "vote " + std::to_string(i) + ": bad public key";
-      return false;
-    }
-    if (!r.bytes(sig, 64) || !r.u64(hqc)) {
-      err = "vote " + std::to_string(i) + ": truncated";
-      return false;
-    }
-    std::memcpy(out.sigs.data() + i * 64, sig, 64);
-    uint8_t *dig = out.digests.data() + i * 32;
-    size_t k = memo_last;
-    if (memo_n == 0 || memo_key[k] != hqc) {
-      for (k = 0; k < memo_n && memo_key[k] != hqc; ++k) {
-      }
-    }
-    if (k < memo_n) {
-      memo_last = k;
-      std::memcpy(dig, memo_dig[k], 32);
-      continue;
-    }
-    uint8_t pre[16], h[64];
-    put_le64(pre, out.round);
-    put_le64(pre + 8, hqc);
-    hsv::sha512_bytes(pre, sizeof(pre), h);
-    std::memcpy(dig, h, 32);
-    if (memo_n < kMemo) {  // beyond kMemo distinct values every new one is hashed
-      memo_key[memo_n] = hqc;
-      std::memcpy(memo_dig[memo_n], h, 32);
-      memo_last = memo_n++;
-    }
-  }
+  // the per-vote digest depends only on (round, high_qc_round): each distinct
+  // one is hashed once (hsvp::TcDigestMemo)
+  hsvp::TcDigestMemo memo(out.round);
+  const bool ok = read_votes<true>(
+      r, out.n, err,
+      [&](size_t n) {
+        out.pks.resize(n * 32);  // every byte is written below
+        out.sigs.resize(n * 64);
+        out.digests.resize(n * 32);
+      },
+      [&](size_t i, uint8_t *&pk, uint8_t *&sig) {
+        pk = out.pks.data() + i * 32;
+        sig = out.sigs.data() + i * 64;
+      },
+      [&](size_t i, uint64_t hqc) { memo.digest(hqc, out.digests.data() + i * 32); });
+  if (!ok) return false;
   if (r.left != 0) {
     err = "trailing bytes after the TC";
     return false;
   }
+  return true;
+}
+
+bool parse_block(const uint8_t *buf, size_t len, BlockParsed &out, std::string &err) {
+  if (!buf && len) {
+    err = "null buffer";
+    return false;
+  }
+  Reader r{buf, len};
+  hsv_proposal &p = out.p;
+  p = hsv_proposal{};
+  if (!read_qc(r, p.qc_hash, p.qc_round, out.qc_votes, p.n_qc, err)) return false;
+  const uint8_t *tag = nullptr;
+  if (!r.bytes(tag, 1)) {
+    err = "truncated Option<TC> tag";
+    return false;
+  }
+  if (*tag > 1) {
+    err = "Option<TC> tag is neither 0 nor 1";
+    return false;
+  }
+  p.has_tc = *tag;
+  if (p.has_tc && !read_tc(r, p.tc_round, out.tc_votes, p.n_tc, err)) return false;
+  uint64_t np = 0;
+  if (!read_public_key(r, p.author)) {
+    err = "author: bad public key";
+    return false;
+  }
+  if (!r.u64(p.round) || !r.u64(np)) {
+    err = "truncated block header";
+    return false;
+  }
+  if (np > r.left / 32) {
+    err = "payload count exceeds the buffer";
+    return false;
+  }
+  p.n_payload = (size_t)np;
+  const uint8_t *pay = nullptr, *sig = nullptr;
+  if (!r.bytes(pay, p.n_payload * 32) || !r.bytes(sig, 64)) {
+    err = "truncated block signature";
+    return false;
+  }
+  out.payload.assign(pay, pay + p.n_payload * 32);
+  std::memcpy(p.signature, sig, 64);
+  if (r.left != 0) {
+    err = "trailing bytes after the block";
+    return false;
+  }
+  p.payload = out.payload.data();
+  p.qc_votes = out.qc_votes.data();
+  p.tc_votes = p.has_tc ? out.tc_votes.data() : nullptr;
+  return true;
+}
+
+bool parse_timeout(const uint8_t *buf, size_t len, TimeoutParsed &out, std::string &err) {
+  if (!buf && len) {
+    err = "null buffer";
+    return false;
+  }
+  Reader r{buf, len};
+  if (!read_qc(r, out.qc_hash, out.qc_round, out.qc_votes, out.n_qc, err)) return false;
+  if (!r.u64(out.round)) {
+    err = "truncated timeout round";
+    return false;
+  }
+  if (!read_public_key(r, out.author)) {
+    err = "author: bad public key";
+    return false;
+  }
+  const uint8_t *sig = nullptr;
+  if (!r.bytes(sig, 64)) {
+    err = "truncated timeout signature";
+    return false;
+  }
+  std::memcpy(out.signature, sig, 64);
+  if (r.left != 0) {
+    err = "trailing bytes after the timeout";
+    return false;
+  }
+  return true;
+}
+
+bool parse_vote(const uint8_t *buf, size_t len, VoteParsed &out, std::string &err) {
+  if (!buf && len) {
+    err = "null buffer";
+    return false;
+  }
+  Reader r{buf, len};
+  const uint8_t *hash = nullptr, *sig = nullptr;
+  if (!r.bytes(hash, 32) || !r.u64(out.round)) {
+    err = "truncated vote header";
+    return false;
+  }
+  std::memcpy(out.hash, hash, 32);
+  if (!read_public_key(r, out.author)) {
+    err = "author: bad public key";
+    return false;
+  }
+  if (!r.bytes(sig, 64)) {
+    err = "truncated vote signature";
+    return false;
+  }
+  std::memcpy(out.signature, sig, 64);
+  if (r.left != 0) {
+    err = "trailing bytes after the vote";
+    return false;
+  }
+  hsvp::qc_digest(out.hash, out.round, out.digest);
   return true;
 }
 

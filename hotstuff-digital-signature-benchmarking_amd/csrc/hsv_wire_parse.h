@@ -1,14 +1,17 @@
-// Parsers of the consensus certificates' bincode bytes (no GPU code): the
-// part of hsv_qc_verify_bincode / hsv_tc_verify_bincode that reads untrusted
-// network bytes (the reference receives them as TCP frames,
-// network/src/receiver.rs:47-60, consensus/src/consensus.rs:32-39).  Kept in
-// its own translation unit so tests/native/wire_fuzz.cpp can build it alone
-// under AddressSanitizer / UndefinedBehaviorSanitizer.
+// Parsers of the consensus messages' bincode bytes (no GPU code): the part of
+// hsv_qc_verify_bincode / hsv_tc_verify_bincode and of the block, timeout and
+// vote calls (hsv_proposal.cpp) that reads untrusted network bytes (the
+// reference receives them as TCP frames, network/src/receiver.rs:47-60,
+// consensus/src/consensus.rs:32-39).  Kept in its own translation unit so
+// tests/native/wire_fuzz.cpp and tests/native/proposal_fuzz.cpp can build it
+// alone under AddressSanitizer / UndefinedBehaviorSanitizer.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include <string>
 #include <vector>
+
+#include "hsv.h"
 
 namespace hsvw {
 
@@ -29,9 +32,37 @@ struct TcParsed {
   size_t n = 0;
 };
 
+// consensus::Block (messages.rs:16-24) as the plain-data proposal of hsv.h;
+// p's pointers point into the vectors beside it (valid until the next parse
+// into this object).
+struct BlockParsed {
+  hsv_proposal p{};
+  std::vector<uint8_t> payload, qc_votes, tc_votes;  // n_payload * 32, n_qc * 96, n_tc * 104
+};
+
+// consensus::Timeout (messages.rs:222-228)
+struct TimeoutParsed {
+  uint8_t author[32], signature[64];
+  uint64_t round = 0;
+  uint8_t qc_hash[32];
+  uint64_t qc_round = 0;
+  std::vector<uint8_t> qc_votes;  // n_qc * 96
+  size_t n_qc = 0;
+};
+
+// consensus::Vote (messages.rs:112-118) and vote.digest() =
+// SHA-512(hash || round_le)[..32] (messages.rs:149-156)
+struct VoteParsed {
+  uint8_t hash[32], author[32], signature[64], digest[32];
+  uint64_t round = 0;
+};
+
 // true on success; on failure `err` says what was malformed
 bool parse_qc(const uint8_t *buf, size_t len, QcParsed &out, std::string &err);
 bool parse_tc(const uint8_t *buf, size_t len, TcParsed &out, std::string &err);
+bool parse_block(const uint8_t *buf, size_t len, BlockParsed &out, std::string &err);
+bool parse_timeout(const uint8_t *buf, size_t len, TimeoutParsed &out, std::string &err);
+bool parse_vote(const uint8_t *buf, size_t len, VoteParsed &out, std::string &err);
 
 // base64 0.13 standard decoding (PublicKey::decode_base64, crypto/src/lib.rs:73-79)
 bool b64_decode(const uint8_t *s, size_t n, std::vector<uint8_t> &out);

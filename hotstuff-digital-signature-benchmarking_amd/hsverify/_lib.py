@@ -107,6 +107,14 @@ def _declare(lib):
                                                           ctypes.c_void_p]),
         "hsv_qc_verify_bincode": (ctypes.c_int, [c_u8p, sz, ctypes.POINTER(ctypes.c_size_t), c_u8p]),
         "hsv_tc_verify_bincode": (ctypes.c_int, [c_u8p, sz, ctypes.POINTER(ctypes.c_size_t), c_u8p]),
+        "hsv_proposal_verify": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_u8p]),
+        "hsv_block_verify_bincode": (ctypes.c_int, [ctypes.c_void_p, c_u8p, sz, ctypes.c_void_p,
+                                                    ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t),
+                                                    c_u8p]),
+        "hsv_timeout_verify_bincode": (ctypes.c_int, [ctypes.c_void_p, c_u8p, sz, ctypes.c_void_p,
+                                                      ctypes.POINTER(ctypes.c_size_t), c_u8p]),
+        "hsv_vote_verify_bincode": (ctypes.c_int, [ctypes.c_void_p, c_u8p, sz]),
+        "hsv_blocks_verify_bincode": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u8p, sz, ctypes.c_void_p]),
         "hsv_set_auto_committee": (ctypes.c_int, [ctypes.c_int]),
         "hsv_set_resident_service": (ctypes.c_int, [ctypes.c_int]),
         "hsv_auto_committee_size": (sz, []),
@@ -183,7 +191,9 @@ def _declare(lib):
                              "hsv_signer_sign_msgs", "hsv_signer_sign_msgs_device",
                              "hsv_committee_verify_transactions", "hsv_committee_verify_transactions_device",
                              "hsv_committee_verify_msgs", "hsv_committee_verify_msgs_device",
-                             "hsv_committee_verify_msgs_indexed", "hsv_committee_verify_msgs_indexed_device"}
+                             "hsv_committee_verify_msgs_indexed", "hsv_committee_verify_msgs_indexed_device",
+                             "hsv_proposal_verify", "hsv_block_verify_bincode", "hsv_timeout_verify_bincode",
+                             "hsv_vote_verify_bincode", "hsv_blocks_verify_bincode"}
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None) if name in optional else getattr(lib, name)
         if fn is None:

@@ -13,6 +13,21 @@ serialises as its base64 string, crypto/src/lib.rs:94-101):
 ``hsv_qc_verify_bincode`` / ``hsv_tc_verify_bincode``, which parse them in C++
 and verify on the GPU (QC: ``verify_batch`` over ``qc.digest()``; TC: one
 strict verification per vote over SHA-512(round_le || high_qc_round_le)[..32]).
+
+The objects that carry them (consensus/src/messages.rs:16-24, 112-118, 222-228):
+
+    Block   = qc | tc: Option<TC> (u8 tag 0 / 1) | author: PublicKey str |
+              round u64 | payload: u64 n, n x Digest (32) | signature R, s
+    Vote    = hash (32) | round u64 | author | signature
+    Timeout = high_qc: QC | round u64 | author | signature
+
+:func:`block_verify`, :func:`timeout_verify`, :func:`vote_verify` and
+:func:`blocks_verify` (a chain) check every signature of the object -- the
+author's (strict), the embedded QC's (batch rule, skipped for the genesis QC)
+and the embedded TC's (strict) -- in ONE verification call and report the
+first failing stage in the reference's order; :func:`proposal_verify` is the
+same for a block given as plain data (``hsv_proposal_verify``).  The stake and
+quorum checks stay with the caller.
 """
 from __future__ import annotations
 
@@ -52,6 +67,150 @@ def encode_tc(round_: int, votes: Sequence[Tuple[bytes, bytes, int]]) -> bytes:
         out.append(bytes(sig))
         out.append(struct.pack("<Q", hqc))
     return b"".join(out)
+
+
+def encode_block(qc: bytes, tc, author: bytes, round_: int, payload: Sequence[bytes], signature: bytes) -> bytes:
+    """bincode of consensus::Block{qc, tc: Option<TC>, author, round, payload:
+    Vec<Digest>, signature} (consensus/src/messages.rs:16-24).  ``qc`` and
+    ``tc`` are their encodings (:func:`encode_qc`, :func:`encode_tc`); ``tc``
+    None is Option::None."""
+    out = [bytes(qc), b"\x00" if tc is None else b"\x01" + bytes(tc), encode_public_key(author),
+           struct.pack("<QQ", round_, len(payload))]
+    out += [bytes(d) for d in payload]
+    out.append(bytes(signature))
+    return b"".join(out)
+
+
+def encode_vote(block_hash: bytes, round_: int, author: bytes, signature: bytes) -> bytes:
+    """bincode of consensus::Vote{hash, round, author, signature} (messages.rs:112-118)."""
+    return bytes(block_hash) + struct.pack("<Q", round_) + encode_public_key(author) + bytes(signature)
+
+
+def encode_timeout(high_qc: bytes, round_: int, author: bytes, signature: bytes) -> bytes:
+    """bincode of consensus::Timeout{high_qc, round, author, signature} (messages.rs:222-228)."""
+    return bytes(high_qc) + struct.pack("<Q", round_) + encode_public_key(author) + bytes(signature)
+
+
+def block_digest(author: bytes, round_: int, payload: Sequence[bytes], qc_hash: bytes) -> bytes:
+    """Block::digest (messages.rs:80-89): what the author signs."""
+    import hashlib
+    return hashlib.sha512(bytes(author) + struct.pack("<Q", round_) + b"".join(bytes(d) for d in payload)
+                          + bytes(qc_hash)).digest()[:32]
+
+
+def vote_digest(block_hash: bytes, round_: int) -> bytes:
+    """Vote::digest and QC::digest (messages.rs:149-156, 201-207)."""
+    import hashlib
+    return hashlib.sha512(bytes(block_hash) + struct.pack("<Q", round_)).digest()[:32]
+
+
+def timeout_digest(round_: int, high_qc_round: int) -> bytes:
+    """Timeout::digest and a TC vote's digest (messages.rs:268-275, 306-313)."""
+    import hashlib
+    return hashlib.sha512(struct.pack("<QQ", round_, high_qc_round)).digest()[:32]
+
+
+# hsv_proposal_result.stage (include/hsv.h)
+STAGE_OK, STAGE_AUTHOR, STAGE_QC, STAGE_TC, STAGE_PARSE = range(5)
+
+
+class ProposalResult(ctypes.Structure):
+    """hsv_proposal_result: the first failing stage and its lowest failing vote."""
+    _fields_ = [("stage", ctypes.c_uint32), ("index", ctypes.c_uint32)]
+
+    def as_tuple(self):
+        return int(self.stage), int(self.index)
+
+
+class Proposal(ctypes.Structure):
+    """hsv_proposal (include/hsv.h): a Block as plain data."""
+    _fields_ = [("author", ctypes.c_uint8 * 32), ("signature", ctypes.c_uint8 * 64), ("round", ctypes.c_uint64),
+                ("payload", ctypes.c_void_p), ("n_payload", ctypes.c_size_t),
+                ("qc_hash", ctypes.c_uint8 * 32), ("qc_round", ctypes.c_uint64),
+                ("qc_votes", ctypes.c_void_p), ("n_qc", ctypes.c_size_t),
+                ("has_tc", ctypes.c_int), ("tc_round", ctypes.c_uint64),
+                ("tc_votes", ctypes.c_void_p), ("n_tc", ctypes.c_size_t)]
+
+
+def _handle(committee):
+    return None if committee is None else committee._h
+
+
+def proposal_verify(author: bytes, signature: bytes, round_: int, payload: Sequence[bytes], qc_hash: bytes,
+                    qc_round: int, qc_votes: Sequence[Tuple[bytes, bytes]], tc_round=None,
+                    tc_votes: Sequence[Tuple[bytes, bytes, int]] = (), committee=None):
+    """hsv_proposal_verify on a block given as plain data (``tc_round`` None:
+    no TC) -> (ok, (stage, index), raw flags of author, QC votes, TC votes)."""
+    lib = _lib.load()
+    pay = np.frombuffer(b"".join(bytes(d) for d in payload), np.uint8)
+    qv = np.frombuffer(b"".join(bytes(pk) + bytes(sig) for pk, sig in qc_votes), np.uint8)
+    tv = np.frombuffer(b"".join(bytes(pk) + bytes(sig) + struct.pack("<Q", h) for pk, sig, h in tc_votes), np.uint8)
+    p = Proposal()
+    p.author[:] = bytes(author)
+    p.signature[:] = bytes(signature)
+    p.round, p.qc_round = round_, qc_round
+    p.qc_hash[:] = bytes(qc_hash)
+    p.payload, p.n_payload = (pay.ctypes.data if pay.size else None), len(payload)
+    p.qc_votes, p.n_qc = (qv.ctypes.data if qv.size else None), len(qc_votes)
+    p.has_tc = 0 if tc_round is None else 1
+    p.tc_round = 0 if tc_round is None else tc_round
+    p.tc_votes, p.n_tc = (tv.ctypes.data if tv.size else None), len(tc_votes)
+    res = ProposalResult()
+    flags = np.zeros(1 + len(qc_votes) + len(tc_votes), np.uint8)
+    rc = _lib.check(lib.hsv_proposal_verify(_handle(committee), ctypes.byref(p), ctypes.byref(res),
+                                            ctypes.c_void_p(flags.ctypes.data)), "hsv_proposal_verify")
+    return rc == 1, res.as_tuple(), flags
+
+
+def block_verify(buf: bytes, committee=None):
+    """Block::verify's signature half in one call (``hsv_block_verify_bincode``)
+    -> (ok, (stage, index), n_qc, n_tc, decoded keys (1 + n_qc + n_tc, 32): the
+    author, the QC voters, the TC voters).  ``committee``: a
+    :class:`hsverify.committee.Committee` (votes verified by member index) or
+    None (the generic path with the automatic cache).  Raises HsvLibraryError
+    on malformed bytes (HSV_ERR_PARSE) or an infrastructure error."""
+    lib = _lib.load()
+    res = ProposalResult()
+    n_qc, n_tc = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    pks = np.zeros((1 + len(buf) // 115, 32), np.uint8)  # a vote is at least 116 encoded bytes
+    rc = _lib.check(lib.hsv_block_verify_bincode(_handle(committee), buf, len(buf), ctypes.byref(res),
+                                                 ctypes.byref(n_qc), ctypes.byref(n_tc),
+                                                 ctypes.c_void_p(pks.ctypes.data)), "hsv_block_verify_bincode")
+    return rc == 1, res.as_tuple(), n_qc.value, n_tc.value, pks[: 1 + n_qc.value + n_tc.value]
+
+
+def timeout_verify(buf: bytes, committee=None):
+    """Timeout::verify's signature half (``hsv_timeout_verify_bincode``)
+    -> (ok, (stage, index), n_qc, decoded keys: the author, then the QC voters)."""
+    lib = _lib.load()
+    res = ProposalResult()
+    n_qc = ctypes.c_size_t(0)
+    pks = np.zeros((1 + len(buf) // 115, 32), np.uint8)
+    rc = _lib.check(lib.hsv_timeout_verify_bincode(_handle(committee), buf, len(buf), ctypes.byref(res),
+                                                   ctypes.byref(n_qc), ctypes.c_void_p(pks.ctypes.data)),
+                    "hsv_timeout_verify_bincode")
+    return rc == 1, res.as_tuple(), n_qc.value, pks[: 1 + n_qc.value]
+
+
+def vote_verify(buf: bytes, committee=None) -> bool:
+    """Vote::verify's signature half (``hsv_vote_verify_bincode``)."""
+    lib = _lib.load()
+    return _lib.check(lib.hsv_vote_verify_bincode(_handle(committee), buf, len(buf)), "hsv_vote_verify_bincode") == 1
+
+
+def blocks_verify(blocks: Sequence[bytes], committee=None):
+    """A chain of blocks in one verification call (``hsv_blocks_verify_bincode``)
+    -> (number of blocks that verify, [(stage, index)] per block); a block
+    that does not parse gets STAGE_PARSE."""
+    lib = _lib.load()
+    offsets = np.zeros(len(blocks) + 1, np.uint64)
+    offsets[1:] = np.cumsum([len(b) for b in blocks], dtype=np.uint64)
+    bufs = b"".join(bytes(b) for b in blocks)
+    results = (ProposalResult * max(1, len(blocks)))()
+    rc = _lib.check(lib.hsv_blocks_verify_bincode(_handle(committee), bufs, ctypes.c_void_p(offsets.ctypes.data),
+                                                  len(blocks), ctypes.cast(results, ctypes.c_void_p)),
+                    "hsv_blocks_verify_bincode")
+    return rc, [results[i].as_tuple() for i in range(len(blocks))]
 
 
 def qc_verify(buf: bytes):

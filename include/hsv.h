@@ -19,6 +19,12 @@
  *   QC / TC signature checks from wire bytes
  *                        consensus/src/messages.rs:180-198, 290-315 -> hsv_qc_verify_bincode,
  *                                                                   hsv_tc_verify_bincode
+ *   Block / Timeout / Vote signature checks, one call each
+ *                        consensus/src/messages.rs:55-76, 250-265, 136-146 -> hsv_proposal_verify,
+ *                                                                   hsv_block_verify_bincode,
+ *                                                                   hsv_blocks_verify_bincode,
+ *                                                                   hsv_timeout_verify_bincode,
+ *                                                                   hsv_vote_verify_bincode
  *
  * Plain pointers and sizes only.  All inputs are borrowed for the duration of
  * the call; the library never retains a caller pointer.  Every entry point is
@@ -110,7 +116,8 @@ HSV_API const char *hsv_last_error(void);
  * hsv_verify_transactions_device) take the optional d_fault argument before
  * `stream`; a caller built against 0.2.x headers must be rebuilt (check
  * HSV_ABI_VERSION against hsv_abi_version() at startup).  Entry points added
- * since (the last: hsv_committee_verify_msgs_indexed*) change no existing signature
+ * since (the last: hsv_proposal_verify and the block, timeout and vote calls
+ * around it) change no existing signature
  * and leave both the version and HSV_ABI_VERSION as they are. */
 #define HSV_ABI_VERSION 3
 HSV_API const char *hsv_version(void);
@@ -484,6 +491,112 @@ HSV_API int hsv_qc_verify_bincode(const uint8_t *buf, size_t len, size_t *n_vote
  * (messages.rs:306-313); 1 iff all pass.  flags_out (optional, one byte per
  * vote): the per-vote HSV_* flags. */
 HSV_API int hsv_tc_verify_bincode(const uint8_t *buf, size_t len, size_t *n_votes_out, uint8_t *flags_out);
+
+/* ---- proposals, votes and timeouts in one call each ----------------------- */
+/* The signature half of Block::verify, Timeout::verify and Vote::verify
+ * (consensus/src/messages.rs:55-76, 250-265, 136-146): every signature of
+ * the object -- the author's, the embedded QC's votes, the embedded TC's
+ * votes -- goes down in ONE verification call, each over its own digest, and
+ * the flags are read back under each stage's own acceptance rule.  The stake,
+ * quorum and authority-reuse checks of the reference (committee.stake,
+ * quorum_threshold, the `used` sets of QC::verify / TC::verify) are NOT done
+ * here: they stay with the caller, as for hsv_qc_verify_bincode and
+ * hsv_tc_verify_bincode, and run before this call as they do in the
+ * reference.
+ *
+ * A proposal as plain data, as a shim fills it from a deserialized Block.
+ * Pointers are borrowed for the call; one whose count is 0 may be NULL. */
+typedef struct hsv_proposal {
+  uint8_t author[32];
+  uint8_t signature[64]; /* R || s */
+  uint64_t round;
+  const uint8_t *payload; /* n_payload * 32 B: the payload digests */
+  size_t n_payload;
+  uint8_t qc_hash[32];
+  uint64_t qc_round;
+  const uint8_t *qc_votes; /* n_qc records of 96 B: pk || R || s */
+  size_t n_qc;
+  int has_tc; /* 0: tc == None */
+  uint64_t tc_round;
+  const uint8_t *tc_votes; /* n_tc records of 104 B: pk || R || s || high_qc_round (u64 LE) */
+  size_t n_tc;
+} hsv_proposal;
+
+/* The verdict in the reference's order: `stage` is the first stage that
+ * fails (author signature, then QC, then TC), `index` the lowest failing vote
+ * of that stage (0 for the author).  For a QC the index is informational:
+ * dalek's verify_batch names no vote. */
+#define HSV_STAGE_OK 0u
+#define HSV_STAGE_AUTHOR 1u
+#define HSV_STAGE_QC 2u
+#define HSV_STAGE_TC 3u
+#define HSV_STAGE_PARSE 4u /* hsv_blocks_verify_bincode only: the block's bytes are malformed */
+typedef struct hsv_proposal_result {
+  uint32_t stage;
+  uint32_t index;
+} hsv_proposal_result;
+
+/* Rules (exactly the reference's):
+ *   author  HSV_STRICT_OK over SHA-512(author || round_le || payload... ||
+ *           qc.hash)[..32] (messages.rs:80-89);
+ *   QC      only if qc != QC::genesis(), and PartialEq compares hash and round
+ *           alone (messages.rs:216-220): a QC with a zero hash and round 0 is
+ *           skipped whatever votes it carries.  Otherwise every vote must have
+ *           (flags & (HSV_PARSE_OK|HSV_EQ_OK)) == both over
+ *           SHA-512(hash || round_le)[..32]; an empty vote list passes;
+ *   TC      if present, every vote HSV_STRICT_OK over
+ *           SHA-512(tc.round_le || high_qc_round_le)[..32].
+ * Returns 1 = Ok (res->stage == HSV_STAGE_OK), 0 = Err (res says where), < 0
+ * an infrastructure error, never a rejection.  res (optional) is written on
+ * 0 and 1 only.
+ * flags_out (optional, 1 + n_qc + n_tc bytes): the items' raw HSV_* flags in
+ * the order author, QC votes, TC votes; the votes of a skipped (genesis) QC
+ * are not verified and read 0.
+ * c == NULL: the items go through hsv_verify with per-item digests -- the
+ * automatic committee cache, the latency forms, the resident service for at
+ * most 4 items.  c != NULL: through hsv_committee_verify by member index; a
+ * key that is not a member of c gets an index >= hsv_committee_size and so
+ * flags 0, a rejection at its stage and index, as the reference rejects a
+ * non-member (UnknownAuthority). */
+HSV_API int hsv_proposal_verify(hsv_committee *c, const hsv_proposal *p, hsv_proposal_result *res,
+                                uint8_t *flags_out);
+
+/* consensus::Block from its bincode bytes (messages.rs:16-24): qc | tc:
+ * Option<TC> (u8 tag 0 / 1) | author: PublicKey str | round: u64 | payload:
+ * Vec<Digest> | signature (64); then hsv_proposal_verify.  Malformed bytes
+ * (truncation, trailing bytes, a count beyond the buffer, bad base64, an
+ * Option tag other than 0 or 1) are HSV_ERR_PARSE, reported before any device
+ * is looked for.  n_qc_out / n_tc_out (optional): the vote counts (n_tc 0
+ * without a TC); pks_out (optional, 32 B each): the decoded keys in the order
+ * author, QC voters, TC voters, for the caller's stake and quorum checks. */
+HSV_API int hsv_block_verify_bincode(hsv_committee *c, const uint8_t *buf, size_t len, hsv_proposal_result *res,
+                                     size_t *n_qc_out, size_t *n_tc_out, uint8_t *pks_out);
+
+/* consensus::Timeout (messages.rs:222-228): high_qc | round | author |
+ * signature.  The author is checked strict over
+ * SHA-512(round_le || high_qc.round_le)[..32] (messages.rs:268-275), high_qc
+ * under the QC rule unless it is genesis; one verification call.  The TC stage
+ * is never reported.  pks_out: author, then the QC voters. */
+HSV_API int hsv_timeout_verify_bincode(hsv_committee *c, const uint8_t *buf, size_t len, hsv_proposal_result *res,
+                                       size_t *n_qc_out, uint8_t *pks_out);
+
+/* consensus::Vote (messages.rs:112-118): hash | round | author | signature,
+ * checked strict over SHA-512(hash || round_le)[..32] (messages.rs:149-156).
+ * c == NULL: routed exactly as hsv_verify_strict; c != NULL: one item by
+ * member index.  1 = Ok, 0 = Err, HSV_ERR_PARSE, other < 0. */
+HSV_API int hsv_vote_verify_bincode(hsv_committee *c, const uint8_t *buf, size_t len);
+
+/* A chain of blocks (a node catching up through the synchronizer): block i is
+ * bufs[offsets[i] .. offsets[i+1]) (n_blocks + 1 non-decreasing offsets, else
+ * HSV_ERR_INVALID_ARG).  All items of all blocks go down in ONE verification
+ * call -- so a long chain takes the pipelined or sharded host path, or the
+ * committee's comb pass when c is given -- and the flags are reduced per block
+ * on the host.  results (optional, n_blocks entries): each block's verdict; a
+ * block whose bytes do not parse gets HSV_STAGE_PARSE and leaves its
+ * neighbours alone.  Returns the number of blocks with HSV_STAGE_OK (0 for
+ * n_blocks == 0), or < 0 for an infrastructure error. */
+HSV_API int hsv_blocks_verify_bincode(hsv_committee *c, const uint8_t *bufs, const uint64_t *offsets,
+                                      size_t n_blocks, hsv_proposal_result *results);
 
 /* ---- signing (host CPU; not on the hot path) ---------------------------- */
 /* Public key for a 32-byte secret seed (dalek Keypair from SecretKey). */

@@ -14,6 +14,11 @@
 //   Signature::verify        -> Result        lib.rs:204-208 (verify_strict semantics)
 //   Signature::verify_batch  -> Result        lib.rs:210-223
 //   SignatureService::request_signature       lib.rs:229-254 -> crypto::SignatureService
+// and, of consensus/src/messages.rs, the signature half of
+//   Block::verify / Vote::verify / Timeout::verify   55-76, 136-146, 250-265
+//                                              -> consensus::Block / Vote / Timeout
+// (one verification call per object: hsv_proposal_verify,
+// hsv_vote_verify_bincode, hsv_timeout_verify_bincode).
 //
 // `Result` carries Ok or Err(CryptoError) exactly like Result<(), CryptoError>.
 // An infrastructure failure (no GPU, HIP error) is NOT an Err: by default it
@@ -381,6 +386,162 @@ class SignatureService {
 };
 
 }  // namespace crypto
+
+// The signature half of the reference's consensus messages
+// (consensus/src/messages.rs): Block::verify, Vote::verify and Timeout::verify
+// with every signature of the object in ONE verification call
+// (hsv_proposal_verify and the calls around it, hsv.h) instead of one call per
+// embedded certificate.  The stake, quorum and authority-reuse checks of the
+// reference stay with the caller and run before these, as in the reference.
+// GPU only: no host route and no fallback, errors throw
+// crypto::InfrastructureError.  `committee` (optional): an hsv_committee whose
+// members the signers are; votes are then verified by member index.
+namespace consensus {
+
+using Round = uint64_t;
+
+// messages.rs:164-169
+struct QC {
+  crypto::Digest hash;
+  Round round = 0;
+  std::vector<std::pair<crypto::PublicKey, crypto::Signature>> votes;
+};
+
+// messages.rs:283-287
+struct TC {
+  Round round = 0;
+  struct Vote {
+    crypto::PublicKey author;
+    crypto::Signature signature;
+    Round high_qc_round = 0;
+  };
+  std::vector<Vote> votes;
+};
+
+// Where a rejected object fails: the first failing stage in the reference's
+// order (HSV_STAGE_AUTHOR, HSV_STAGE_QC, HSV_STAGE_TC) and its lowest failing vote.
+struct Verdict {
+  crypto::Result result = crypto::Result::ok();
+  hsv_proposal_result where{HSV_STAGE_OK, 0};
+  bool is_ok() const { return result.is_ok(); }
+};
+
+namespace detail {
+inline void put_u64(std::vector<uint8_t> &b, uint64_t v) {
+  for (int i = 0; i < 8; ++i) b.push_back((uint8_t)(v >> (8 * i)));
+}
+// bincode of PublicKey: its base64 string
+inline void put_key(std::vector<uint8_t> &b, const crypto::PublicKey &pk) {
+  const std::string s = pk.encode_base64();
+  put_u64(b, s.size());
+  b.insert(b.end(), s.begin(), s.end());
+}
+inline void put_signature(std::vector<uint8_t> &b, const crypto::Signature &s) {
+  b.insert(b.end(), s.part1.begin(), s.part1.end());
+  b.insert(b.end(), s.part2.begin(), s.part2.end());
+}
+inline void put_qc(std::vector<uint8_t> &b, const QC &qc) {
+  b.insert(b.end(), qc.hash.bytes.begin(), qc.hash.bytes.end());
+  put_u64(b, qc.round);
+  put_u64(b, qc.votes.size());
+  for (const auto &v : qc.votes) {
+    put_key(b, v.first);
+    put_signature(b, v.second);
+  }
+}
+inline Verdict verdict(int rc, const hsv_proposal_result &where, const char *what) {
+  crypto::check_infra(rc, what);
+  Verdict v;
+  v.result = rc == 1 ? crypto::Result::ok() : crypto::Result::err();
+  v.where = where;
+  return v;
+}
+}  // namespace detail
+
+// messages.rs:16-24
+struct Block {
+  QC qc;
+  bool has_tc = false;  // tc: Option<TC>
+  TC tc;
+  crypto::PublicKey author;
+  Round round = 0;
+  std::vector<crypto::Digest> payload;
+  crypto::Signature signature;
+
+  // Block::verify's signature checks (messages.rs:63-74): fills an
+  // hsv_proposal and makes one call.
+  Verdict verify_signatures(hsv_committee *committee = nullptr) const {
+    std::vector<uint8_t> pay(payload.size() * 32), qv(qc.votes.size() * 96), tv(has_tc ? tc.votes.size() * 104 : 0);
+    for (size_t i = 0; i < payload.size(); ++i) std::memcpy(pay.data() + 32 * i, payload[i].bytes.data(), 32);
+    for (size_t i = 0; i < qc.votes.size(); ++i) {
+      std::memcpy(qv.data() + 96 * i, qc.votes[i].first.bytes.data(), 32);
+      std::memcpy(qv.data() + 96 * i + 32, qc.votes[i].second.flatten().data(), 64);
+    }
+    for (size_t i = 0; i * 104 < tv.size(); ++i) {
+      uint8_t *r = tv.data() + 104 * i;
+      std::memcpy(r, tc.votes[i].author.bytes.data(), 32);
+      std::memcpy(r + 32, tc.votes[i].signature.flatten().data(), 64);
+      for (int b = 0; b < 8; ++b) r[96 + b] = (uint8_t)(tc.votes[i].high_qc_round >> (8 * b));
+    }
+    hsv_proposal p{};
+    std::memcpy(p.author, author.bytes.data(), 32);
+    std::memcpy(p.signature, signature.flatten().data(), 64);
+    p.round = round;
+    p.payload = pay.data();
+    p.n_payload = payload.size();
+    std::memcpy(p.qc_hash, qc.hash.bytes.data(), 32);
+    p.qc_round = qc.round;
+    p.qc_votes = qv.data();
+    p.n_qc = qc.votes.size();
+    p.has_tc = has_tc ? 1 : 0;
+    p.tc_round = tc.round;
+    p.tc_votes = tv.data();
+    p.n_tc = has_tc ? tc.votes.size() : 0;
+    hsv_proposal_result where{HSV_STAGE_OK, 0};
+    return detail::verdict(hsv_proposal_verify(committee, &p, &where, nullptr), where, "hsv_proposal_verify");
+  }
+};
+
+// messages.rs:112-118
+struct Vote {
+  crypto::Digest hash;
+  Round round = 0;
+  crypto::PublicKey author;
+  crypto::Signature signature;
+
+  // Vote::verify's signature check (messages.rs:143-145), from the vote's bincode bytes
+  crypto::Result verify_signature(hsv_committee *committee = nullptr) const {
+    std::vector<uint8_t> b(hash.bytes.begin(), hash.bytes.end());
+    detail::put_u64(b, round);
+    detail::put_key(b, author);
+    detail::put_signature(b, signature);
+    const int rc = crypto::check_infra(hsv_vote_verify_bincode(committee, b.data(), b.size()), "hsv_vote_verify_bincode");
+    return rc == 1 ? crypto::Result::ok() : crypto::Result::err();
+  }
+};
+
+// messages.rs:222-228
+struct Timeout {
+  QC high_qc;
+  Round round = 0;
+  crypto::PublicKey author;
+  crypto::Signature signature;
+
+  // Timeout::verify's signature checks (messages.rs:257-263) in one call,
+  // from the timeout's bincode bytes; the TC stage is never reported
+  Verdict verify_signatures(hsv_committee *committee = nullptr) const {
+    std::vector<uint8_t> b;
+    detail::put_qc(b, high_qc);
+    detail::put_u64(b, round);
+    detail::put_key(b, author);
+    detail::put_signature(b, signature);
+    hsv_proposal_result where{HSV_STAGE_OK, 0};
+    return detail::verdict(hsv_timeout_verify_bincode(committee, b.data(), b.size(), &where, nullptr, nullptr), where,
+                           "hsv_timeout_verify_bincode");
+  }
+};
+
+}  // namespace consensus
 
 // Batch key derivation and signing on the GPU (hsv_signer_*, hsv.h): the form
 // of generate_keypair / Signature::new a load generator uses.  Not constant
