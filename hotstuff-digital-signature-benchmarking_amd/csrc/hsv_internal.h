@@ -64,6 +64,13 @@ int hsvi_set_inject(int mode);
 // Lattice bound of the comb-path prepass (tests; 0 = default); returns the
 // previous bound or -1.
 int hsvi_set_lattice_bits(int bits);
+// Dealing by column count in the two-launch point pass (tests and A/B runs;
+// hsv_kernels.hip), for the calling thread's launches: bit 0 on (the default),
+// off = index order; bit 1: keep each launch's class counts, which
+// hsvi_deal_counts reports (out[0] >= 67 columns .. out[5] <= 62).
+// hsvi_set_deal returns the previous mode, or -1.
+int hsvi_set_deal(int mode);
+int hsvi_deal_counts(uint32_t out[6]);
 // The bound in force, and a fresh canary nonce (odd, never 0): what launch_hp
 // hands its kernels, for the launchers of hsv_small.hip and hsv_mempool.hip.
 int hsvi_lattice_bits(void);
@@ -287,8 +294,8 @@ int hsvi_set_msgs_small(int mode);
 int hsvi_msgs_form_counts(uint64_t out[5]);
 hipError_t hsv_launch_msg_prep(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, uint64_t sig_stride,
                                const uint8_t *msgs, const uint64_t *offsets, uint64_t msg_len, uint64_t msg_stride,
-                               uint32_t n, uint32_t *prep, uint32_t *fb_count, uint32_t *fb_list, int lat_bits,
-                               hipStream_t stream);
+                               uint32_t n, uint32_t *prep, void *ctr, uint32_t *fb_list, uint32_t *cls_list,
+                               int lat_bits, hipStream_t stream);
 // One round (n <= 2^22) of hsv_committee_verify_msgs* (hsv_committee_msgs.hip):
 // the messages of hsv_launch_verify_msgs with the committee arguments of
 // hsv_launch_committee_tx.  Three launches on `stream`: the route kernel (the

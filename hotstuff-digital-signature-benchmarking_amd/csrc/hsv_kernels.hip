@@ -35,24 +35,32 @@ __device__ uint64_t g_phase_clk[kPhaseCap * 8];
 
 // Two-pass form (hsv_verify_hc.hpp, prep_scalars / verify_one_prepped).
 // Pass 1: one lane per item, scalar work only; records to `rec` (SoA, row
-// stride n), fallback items appended to fb_list.
+// stride n), fallback items appended to fb_list, every other item to the list
+// of its column class (deal_append, hsv_pointpass.hpp; cls_list null: no lists,
+// the point pass runs in index order).
 template <int WA>
 __global__ void __launch_bounds__(kBlock)
 hsv_prep_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const uint8_t *__restrict__ sig,
                 uint64_t sig_stride, const uint8_t *__restrict__ msg, uint64_t msg_stride, uint32_t n,
                 uint32_t *__restrict__ rec, HcCounters *__restrict__ ctr, uint32_t *__restrict__ fb_list,
-                int lat_bits) {
+                uint32_t *__restrict__ cls_list, int lat_bits) {
   // The prepass usually runs beside the previous batch's point pass (another
   // stream, or the previous chunk of a host pipeline), whose waves keep every
   // SIMD's VALU busy; this batch's point pass cannot start before the prepass
   // ends.  Highest wave priority: the SIMD issues the prepass's waves first.
   __builtin_amdgcn_s_setprio(3);
   const uint32_t idx = blockIdx.x * kBlock + threadIdx.x;
-  if (idx >= n) return;
-  uint32_t pkw[8], sigw[16], msgw[8];
-  load_triple(pk, pk_stride, sig, sig_stride, msg, msg_stride, idx, pkw, sigw, msgw);
-  if (prep_scalars<WA, PutPlain, pointpass_digit_bits<WA>()>(pkw, sigw, msgw, rec + idx, n, lat_bits))
-    fb_list[atomicAdd(&ctr->fb_count, 1u)] = idx;
+  bool listed = false;
+  uint32_t cls = 0;
+  if (idx < n) {
+    uint32_t pkw[8], sigw[16], msgw[8];
+    load_triple(pk, pk_stride, sig, sig_stride, msg, msg_stride, idx, pkw, sigw, msgw);
+    const bool fb =
+        prep_scalars<WA, PutPlain, pointpass_digit_bits<WA>()>(pkw, sigw, msgw, rec + idx, n, lat_bits, &cls);
+    if (fb) fb_list[atomicAdd(&ctr->fb_count, 1u)] = idx;
+    listed = !fb;
+  }
+  if (cls_list) deal_append(ctr, cls_list, n, listed, cls, idx);  // the whole block: barriers inside
 }
 
 // Pass 2: persistent grid, 64-item batches from ctr->next over a virtual
@@ -60,6 +68,12 @@ hsv_prep_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const uint8_
 // the full-length path; in the regular range a fallback item's lane computes
 // nothing it stores.  strict_bits is zeroed before the launch and every
 // batch ORs its bits in (a word can receive bits from both ranges).
+// Dealt (cls_list not null, the default): the regular range is the prepass's
+// class lists end to end, longest column need first, without the fallback
+// items; a batch is 64 consecutive positions of it, the lane's item comes
+// from the list, and a lane past the end redoes the batch's first item and
+// stores nothing.  A batch's items then share no strict_bits words: one
+// atomicOr per accepted item, as the fallback range.
 // KREC (messages of any length, hsv_launch_verify_msgs): the prepass
 // (hsv_msg_prep_kernel, hsv_msgs.hip) has hashed the whole message, and this
 // pass never touches message bytes (msg is unused): a fallback item's k mod l
@@ -72,8 +86,8 @@ hsv_verify_hp_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const u
                      uint8_t *__restrict__ flags_out, uint32_t *__restrict__ strict_bits,
                      uint4 *__restrict__ vt_ws, const uint32_t *__restrict__ comb_b,
                      const uint32_t *__restrict__ rec, HcCounters *__restrict__ ctr,
-                     const uint32_t *__restrict__ fb_list, uint32_t *__restrict__ canary, uint32_t nonce,
-                     uint32_t inject, uint32_t *__restrict__ fault) {
+                     const uint32_t *__restrict__ fb_list, const uint32_t *__restrict__ cls_list,
+                     uint32_t *__restrict__ canary, uint32_t nonce, uint32_t inject, uint32_t *__restrict__ fault) {
   constexpr bool JOINT = joint_pointpass<WA>();
   const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
   PointPassTab<WA> vt{vt_ws + (uint64_t)slot * pointpass_lane_uint4<WA>(), inject};
@@ -83,6 +97,9 @@ hsv_verify_hp_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const u
   const uint32_t nfb = __builtin_amdgcn_readfirstlane(ctr->fb_count);
   const uint32_t fb_end = (nfb + 63u) & ~63u;
   const uint32_t words = (n + 31u) / 32u;
+  const bool deal = cls_list != nullptr;
+  const DealOffsets off(ctr);
+  const uint32_t nreg = deal ? off.total() : n;  // length of the regular range
 #ifdef HSV_PHASE_CLOCKS
   uint32_t nbw = 0;  // batches this wave has taken
 #endif
@@ -90,7 +107,7 @@ hsv_verify_hp_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const u
     uint32_t base = 0;
     if (lane == 0) base = atomicAdd(&ctr->next, 64u);
     base = __builtin_amdgcn_readfirstlane(__shfl(base, 0));
-    if (base >= fb_end + n) break;
+    if (base >= fb_end + nreg) break;
     if (inject == kInjectCanary) canary[slot] = ~nonce;
     if (base < fb_end) {
       const uint32_t j = base + lane;
@@ -106,9 +123,9 @@ hsv_verify_hp_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const u
       continue;
     }
     const uint32_t b0 = base - fb_end;
-    const uint32_t idx = b0 + lane;
-    const bool valid = idx < n;
-    const uint32_t li = valid ? idx : n - 1u;
+    const bool valid = b0 + lane < nreg;
+    const uint32_t pos = valid ? b0 + lane : b0;
+    const uint32_t li = deal ? min(off.item(cls_list, n, pos), n - 1u) : pos;
     uint32_t pkw[8], rw[8];
     load_words8(pk + (uint64_t)li * pk_stride, pkw);
     load_words8(sig + (uint64_t)li * sig_stride, rw);
@@ -137,8 +154,10 @@ hsv_verify_hp_kernel(const uint8_t *__restrict__ pk, uint64_t pk_stride, const u
 #endif
     bad |= ((f & kFault) ? 1u : 0u) | (canary[slot] != nonce ? 2u : 0u);
     const uint32_t fo = KREC && (meta & kPrepVoid) ? 0u : f;
-    if (own && flags_out) flags_out[idx] = (uint8_t)fo;
-    if (strict_bits) {
+    if (own && flags_out) flags_out[li] = (uint8_t)fo;
+    if (deal) {
+      if (own && strict_bits && (fo & kStrictOk)) atomicOr(&strict_bits[li >> 5], 1u << (li & 31u));
+    } else if (strict_bits) {
       const uint64_t mask = __ballot(own && (fo & kStrictOk));
       const uint32_t w = b0 / 32u + lane;
       const uint32_t part = lane ? (uint32_t)(mask >> 32) : (uint32_t)mask;
@@ -311,6 +330,16 @@ std::atomic<int> g_lat_bits{hsv::kLatCombBits};
 // test that injects on one thread leaves every other thread's calls alone.
 thread_local uint32_t t_inject = hsv::kInjectNone;
 
+// Dealing by column count in the calling thread's two-launch point passes
+// (hsvi_set_deal; only libhsv_test.so exports a setter): bit 0 on (the
+// default), off = index order, for parity tests and A/B runs; bit 1: each such
+// launch waits for its stream and keeps its class counts (hsvi_deal_counts).
+#ifndef HSV_DEAL_DEFAULT  // 0: A/B builds in index order (tools/build_ab_libs.sh)
+#define HSV_DEAL_DEFAULT 1
+#endif
+thread_local int t_deal = HSV_DEAL_DEFAULT;
+thread_local uint32_t t_deal_counts[hsv::kColClasses] = {};
+
 // HSV_TX_FUSED=0: transactions as the record kernel + point pass pair (the
 // round-5 form), for A/B runs; read once per process.
 bool tx_fused_enabled() {
@@ -329,7 +358,7 @@ uint32_t next_nonce() {
 
 
 // Two-pass launch (variants 19/20): prepass over all items, then the
-// persistent point pass.  Workspace: per-lane tables | counters (256 B) |
+// persistent point pass.  Workspace: per-lane tables | counters (kCtrBytes) |
 // fallback list (4 B per item) | prep records (kPrepWords x 4 B per item).
 // Transactions whose records the prepass writes itself (hsv_launch_tx_prep):
 // the point pass then reads pk / R (and, for fallback items, s and the
@@ -397,7 +426,13 @@ hipError_t launch_hp(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, 
   const size_t fb_bytes = (size_t)n * sizeof(uint32_t);
   const size_t rec_bytes = (size_t)n * hsv::kPrepWords * sizeof(uint32_t);
   const size_t ready_bytes = fused ? (((size_t)(n + 63u) / 64u) * sizeof(uint32_t) + 255) & ~(size_t)255 : 0;
-  const size_t need = ws_bytes + 256 + canary_bytes + fb_bytes + rec_bytes + ready_bytes;
+  // class lists of the dealt point pass (one of n entries per class: an item
+  // sits on one of them).  The transaction forms keep index order: the fused
+  // launch ties point batches to record batches, and the pair's record kernel
+  // keeps no lists.  The size does not depend on the test switch.
+  const bool lists = !tx && hsv::joint_pointpass<WA>();
+  const size_t cls_bytes = lists ? (size_t)n * hsv::kColClasses * sizeof(uint32_t) : 0;
+  const size_t need = ws_bytes + hsv::kCtrBytes + canary_bytes + fb_bytes + rec_bytes + ready_bytes + cls_bytes;
   if (ws_need) {  // size query only
     *ws_need = need;
     return hipSuccess;
@@ -407,10 +442,13 @@ hipError_t launch_hp(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, 
   uint8_t *ws8 = ws.get();
   uint4 *vt_ws = reinterpret_cast<uint4 *>(ws8);
   hsv::HcCounters *ctr = reinterpret_cast<hsv::HcCounters *>(ws8 + ws_bytes);
-  uint32_t *canary = reinterpret_cast<uint32_t *>(ws8 + ws_bytes + 256);
-  uint32_t *fb_list = reinterpret_cast<uint32_t *>(ws8 + ws_bytes + 256 + canary_bytes);
-  uint32_t *rec = reinterpret_cast<uint32_t *>(ws8 + ws_bytes + 256 + canary_bytes + fb_bytes);
-  uint32_t *ready = reinterpret_cast<uint32_t *>(ws8 + ws_bytes + 256 + canary_bytes + fb_bytes + rec_bytes);
+  uint8_t *p = ws8 + ws_bytes + hsv::kCtrBytes;
+  uint32_t *canary = reinterpret_cast<uint32_t *>(p);
+  uint32_t *fb_list = reinterpret_cast<uint32_t *>(p += canary_bytes);
+  uint32_t *rec = reinterpret_cast<uint32_t *>(p += fb_bytes);
+  uint32_t *ready = reinterpret_cast<uint32_t *>(p += rec_bytes);
+  uint32_t *cls_list = reinterpret_cast<uint32_t *>(p += ready_bytes);
+  if (!lists || !(t_deal & 1)) cls_list = nullptr;  // index order
   e = hipMemsetAsync(ctr, 0, sizeof(hsv::HcCounters), stream);
   if (e == hipSuccess && strict_bits) e = hipMemsetAsync(strict_bits, 0, (size_t)((n + 31u) / 32u) * 4u, stream);
   if (e == hipSuccess && fused) {
@@ -432,23 +470,29 @@ hipError_t launch_hp(const uint8_t *pk, uint64_t pk_stride, const uint8_t *sig, 
   } else if (e == hipSuccess && mp) {
     static_assert(WA == 4, "hsv_launch_msg_prep writes the WA = 4 point pass's prepass record");
     e = hsv_launch_msg_prep(pk, pk_stride, sig, sig_stride, mp->msgs, mp->offsets, mp->msg_len, mp->msg_stride, n,
-                            rec, &ctr->fb_count, fb_list, g_lat_bits.load(), stream);
+                            rec, ctr, fb_list, cls_list, g_lat_bits.load(), stream);
   } else if (e == hipSuccess) {
     hipLaunchKernelGGL((hsv::hsv_prep_kernel<WA>), dim3(blocks_needed), dim3(hsv::kBlock), 0, stream, pk, pk_stride,
-                       sig, sig_stride, msg, msg_stride, n, rec, ctr, fb_list, g_lat_bits.load());
+                       sig, sig_stride, msg, msg_stride, n, rec, ctr, fb_list, cls_list, g_lat_bits.load());
     e = hipGetLastError();
   }
   if (e == hipSuccess) {
     if (mp) {
       hipLaunchKernelGGL((hsv::hsv_verify_hp_kernel<WA, WAVES, CB, true>), dim3(grid), dim3(hsv::kBlock), 0, stream,
                          pk, pk_stride, sig, sig_stride, nullptr, 0, n, flags_out, strict_bits, vt_ws, comb_b, rec,
-                         ctr, fb_list, canary, next_nonce(), t_inject, fault);
+                         ctr, fb_list, cls_list, canary, next_nonce(), t_inject, fault);
     } else {
       hipLaunchKernelGGL((hsv::hsv_verify_hp_kernel<WA, WAVES, CB>), dim3(grid), dim3(hsv::kBlock), 0, stream, pk,
                          pk_stride, sig, sig_stride, msg, msg_stride, n, flags_out, strict_bits, vt_ws, comb_b, rec,
-                         ctr, fb_list, canary, next_nonce(), t_inject, fault);
+                         ctr, fb_list, cls_list, canary, next_nonce(), t_inject, fault);
     }
     e = hipGetLastError();
+  }
+  if (e == hipSuccess && (t_deal & 2)) {  // test hook: this launch's class counts, read back before the block is freed
+    hsv::HcCounters h;
+    e = hipMemcpyAsync(&h, ctr, sizeof(h), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    for (int k = 0; e == hipSuccess && k < hsv::kColClasses; ++k) t_deal_counts[k] = h.cls[k].count;
   }
   return ws.done(e);
 }
@@ -634,6 +678,25 @@ extern "C" int hsvi_set_inject(int mode) {
   return prev;
 }
 extern "C" int hsvi_inject_mode(void) { return (int)t_inject; }
+
+// Dealing mode of the calling thread's following two-launch point passes: bit 0
+// deal by column count (off: index order), bit 1 keep each launch's class
+// counts for hsvi_deal_counts (the launch then waits for its stream).  The
+// default is 1.  Returns the previous mode, or -1 for an unknown one.
+extern "C" int hsvi_set_deal(int mode) {
+  if (mode < 0 || mode > 3) return -1;
+  const int prev = t_deal;
+  t_deal = mode;
+  return prev;
+}
+// Items per column class (hsv_verify_hc.hpp col_class: out[0] needs >= 67
+// columns .. out[5] at most 62) of the calling thread's last launch under mode
+// bit 1; all zero when that launch ran in index order.
+extern "C" int hsvi_deal_counts(uint32_t out[6]) {
+  static_assert(hsv::kColClasses == 6, "hook signature");
+  for (int i = 0; i < hsv::kColClasses; ++i) out[i] = t_deal_counts[i];
+  return 0;
+}
 // for the launchers of other translation units (hsv_small.hip, hsv_mempool.hip)
 extern "C" int hsvi_lattice_bits(void) { return g_lat_bits.load(); }
 extern "C" uint32_t hsvi_next_nonce(void) { return next_nonce(); }

@@ -184,7 +184,9 @@ __device__ __forceinline__ uint32_t verify_fallback_item(const uint8_t *pk, uint
   }
 }
 
-// Work counters of the comb kernels, zeroed before the launch (32 bytes).
+// Work counters of the comb kernels, zeroed before the launch (kCtrBytes
+// reserved).  The class counters sit on 128-byte lines of their own: every
+// block of a prepass adds to them while the launch runs.
 struct HcCounters {
   uint32_t next;      // main pass: next item handed out
   uint32_t fb_count;  // deferred full-length items appended to fb_list
@@ -192,7 +194,78 @@ struct HcCounters {
   uint32_t pad;
   uint32_t rnext;     // fused transaction launch: next 64-transaction record batch handed out
   uint32_t rdone;     // fused transaction launch: record batches published
-  uint32_t pad2[2];
+  uint32_t pad2[26];
+  struct Line {
+    uint32_t count;
+    uint32_t pad[31];
+  } cls[kColClasses];  // dealt point pass: items on each column class's list (deal_append)
+};
+constexpr size_t kCtrBytes = 1024;
+static_assert(sizeof(HcCounters) == 128 * (1 + kColClasses) && sizeof(HcCounters) <= kCtrBytes, "counter block");
+
+// Dealing by column count (hsv_prep_kernel, hsv_msg_prep_kernel ->
+// hsv_verify_hp_kernel).  The prepass appends every item that is not a
+// fallback item to the list of its class (col_class, hsv_verify_hc.hpp): list
+// k is cls_list + k * n, its length ctr->cls[k].count.  A wave finds its items
+// of a class with one ballot and reserves their places in the block's count
+// (LDS); the block then adds each class's count to the global counter once:
+// one global atomic per class and block, not per lane or wave.
+// The point pass then walks [fallback items | list 0 | list 1 | ...], longest
+// need first: a 64-item batch holds items of one column count (two where it
+// straddles a class boundary), so the wave-uniform column loop of
+// straus_joint runs what its items need and not the count of the one long
+// scalar in 60 that index order puts into most waves.
+// Every thread of the block calls (two barriers inside); on: this lane has an
+// item to append.
+__device__ __forceinline__ void deal_append(HcCounters *ctr, uint32_t *cls_list, uint32_t n, bool on, uint32_t cls,
+                                            uint32_t idx) {
+  __shared__ uint32_t s_count[kColClasses], s_base[kColClasses];
+  const uint32_t lane = threadIdx.x & 63u;
+  if (threadIdx.x < (uint32_t)kColClasses) s_count[threadIdx.x] = 0u;
+  __syncthreads();
+  uint32_t at = 0;  // this lane's place among the block's items of its class
+  HSV_UNROLL
+  for (uint32_t k = 0; k < (uint32_t)kColClasses; ++k) {
+    const uint64_t m = __ballot(on && cls == k);
+    if (m == 0) continue;
+    const uint32_t lead = (uint32_t)__ffsll((unsigned long long)m) - 1u;
+    uint32_t base = 0;
+    if (lane == lead) base = atomicAdd(&s_count[k], (uint32_t)__popcll(m));
+    base = (uint32_t)__shfl((int)base, (int)lead);
+    if (on && cls == k) at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+  }
+  __syncthreads();
+  if (threadIdx.x < (uint32_t)kColClasses) {
+    const uint32_t c = s_count[threadIdx.x];
+    s_base[threadIdx.x] = c ? atomicAdd(&ctr->cls[threadIdx.x].count, c) : 0u;
+  }
+  __syncthreads();
+  if (on) cls_list[(uint64_t)cls * n + s_base[cls] + at] = idx;
+}
+
+// The dealt range's item at position p (< the lists' total length): prefix
+// offsets from the counters, wave-uniform; the class is found per lane.
+struct DealOffsets {
+  uint32_t end[kColClasses];  // end[k] = cls[0] + .. + cls[k]
+  __device__ __forceinline__ explicit DealOffsets(const HcCounters *ctr) {
+    uint32_t s = 0;
+    HSV_UNROLL
+    for (int k = 0; k < kColClasses; ++k) {
+      s += __builtin_amdgcn_readfirstlane(ctr->cls[k].count);
+      end[k] = s;
+    }
+  }
+  __device__ __forceinline__ uint32_t total() const { return end[kColClasses - 1]; }
+  __device__ __forceinline__ uint32_t item(const uint32_t *cls_list, uint32_t n, uint32_t p) const {
+    uint32_t k = 0, lo = 0;
+    HSV_UNROLL
+    for (int c = 0; c + 1 < kColClasses; ++c) {
+      const bool past = p >= end[c];
+      k = past ? (uint32_t)c + 1u : k;
+      lo = past ? end[c] : lo;
+    }
+    return cls_list[(uint64_t)k * n + (p - lo)];
+  }
 };
 
 // Device self-checks of the product kernels (a device failure must

@@ -21,6 +21,8 @@ int hsv_test_lanesplit_check(const uint32_t *in, uint32_t rows, uint32_t *out) {
 int hsv_test_field_ops(const uint32_t *in, uint32_t n, uint32_t *out) { return hsvi_test_field_ops(in, n, out); }
 int hsv_test_scalar_ops(const uint32_t *in, uint32_t n, uint32_t *out) { return hsvi_test_scalar_ops(in, n, out); }
 int hsv_set_lattice_bits(int bits) { return hsvi_set_lattice_bits(bits); }
+int hsv_test_deal(int mode) { return hsvi_set_deal(mode); }
+int hsv_test_deal_counts(uint32_t out[6]) { return out ? hsvi_deal_counts(out) : HSV_ERR_INVALID_ARG; }
 int hsv_set_variant(int variant) { return hsvi_set_variant(variant); }
 int hsv_variant_list(int *out, int cap) { return hsvi_variant_list(out, cap); }
 int hsv_variant_available(int variant) { return hsvi_variant_available(variant); }

@@ -41,6 +41,18 @@ HSV_API int hsv_test_scalar_ops(const uint32_t *in, uint32_t n, uint32_t *out);
 /* Lattice bound of the comb-path prepass (0 = default 138; 133 sends the
  * lattice-fallback fixtures down the full-length path); previous bound or -1. */
 HSV_API int hsv_set_lattice_bits(int bits);
+/* Tests and A/B runs: how the CALLING THREAD's following two-launch point
+ * passes (above 2^13 items: hsv_verify_device, hsv_verify_msgs*) take their
+ * batches.  Bit 0: dealt by column count (the default, 1); clear: index
+ * order, the same flags.  Bit 1: each such launch waits for its stream and
+ * keeps the lengths of its class lists for hsv_test_deal_counts.  Returns the
+ * previous mode, or -1 for an unknown one. */
+HSV_API int hsv_test_deal(int mode);
+/* Items per column class of the calling thread's last launch under bit 1:
+ * out[0] those that need >= 67 columns, out[1] 66, ... out[5] at most 62
+ * (fallback items are on no list; all zero after an index-order launch).
+ * HSV_OK. */
+HSV_API int hsv_test_deal_counts(uint32_t out[6]);
 /* Kernel variant of the following calls (the ids hsv_variant_list reports). */
 HSV_API int hsv_set_variant(int variant);
 HSV_API int hsv_variant_list(int *out, int cap);

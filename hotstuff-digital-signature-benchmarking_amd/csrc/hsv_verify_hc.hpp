@@ -18,8 +18,8 @@
 // The throughput point pass (hsv_verify_hp_kernel, the fused transaction
 // launch) runs phase 1 over ONE joint table instead (jt_build, straus_joint,
 // the JOINT form of verify_one_prepped): the 12 lines i(-R) + j(-A) of the
-// sign-folded pairs of signed radix-4 digits, 70 columns of 2 bits with two
-// doublings and one cached addition each -- the same doublings and additions
+// sign-folded pairs of signed radix-4 digits in {-1 .. 2}, 70 columns of 2 bits
+// with two doublings and one cached addition each -- the same doublings and additions
 // per bit, four table lines fewer to build, pack, store and read back.  Its
 // prepasses write the record's digits as 2-bit columns (prep_from_hash, DW = 2).
 // The latency forms and the committee kernels keep the two 4-bit tables.
@@ -262,24 +262,80 @@ struct PutPlain {
 // malformed) gets the meta word kPrepVoid alone: the point pass answers flags 0.
 // DW: the digit width of the record's ten digit words.  DW = WA is the format
 // of straus_vt (NW windows of WA bits); DW = 2 the joint point pass's: 70
-// columns of signed radix-4 digits chunk - 2 in {-2, -1, 0, 1}, top-aligned in
-// the same five words (straus_joint).  Nothing else in the record depends on it.
+// columns of signed radix-4 digits chunk - 1 in {-1, 0, 1, 2}, top-aligned in
+// the same five words (recode_cols, straus_joint).  Nothing else in the record
+// depends on it.
+// need (DW = 2 only): where given, the item's column class (col_class), by
+// which hsv_verify_hp_kernel deals its batches.
 constexpr uint32_t kPrepVoid = 8u;
-// c + C_2 < 2^140 needs c < 2^140 / 3: the 138-bit lattice bound leaves room
+
+// ---- 2-bit columns, digits in {-1 .. 2} ---------------------------------------
+// The scalars are magnitudes (|c0| >= 0, c1 > 0), so the digit set leans to
+// the positive side: m columns of digits in {-1 .. 2} reach 2 (4^m - 1) / 3,
+// one bit more than the symmetric {-2 .. 1} of recode_top5<2>, and the
+// wave-uniform skip of leading zero columns (straus_joint) drops about half a
+// column more per wave (tools/lattice_bits.py).  Adding C = (4^NW - 1) / 3,
+// chunks 0b01 .. 01, makes chunk t of the sum the digit plus kColOffset.
+constexpr int kColOffset = 1;
+HSV_INL constexpr uint32_t col_const_limb(int nw, int j) {
+  uint32_t r = 0;
+  for (int b = 0; b < 32; b += 2)
+    if (32 * j + b < 2 * nw) r |= 1u << b;
+  return r;
+}
+// c < 2^138 gives c + C < 2^138 + 4^70 / 3 < 4^70
 static_assert(kLatCombBits + 2 <= HalfCombWindows<2>::BITS && HalfCombWindows<2>::NW == 70,
-              "2-bit columns: c < 2^138 plus the recoding constant (0.667 * 2^140) must stay below 2^140");
+              "2-bit columns: c < 2^138 plus the recoding constant (4^70 - 1) / 3 must stay below 4^70");
+// x (5 limbs) + C over NW columns, the top column at the top bit of 5 limbs
+template <int NW>
+HSV_INL void recode_cols(const uint32_t x[5], uint32_t out[5]) {
+  uint64_t t = 0;
+  HSV_UNROLL
+  for (int j = 0; j < 5; ++j) {
+    t += (uint64_t)x[j] + col_const_limb(NW, j);
+    out[j] = (uint32_t)t;
+    t >>= 32;
+  }
+  limbs_shl_const<5, 160 - 2 * NW>(out);
+}
+
+// Columns a scalar needs: cols(c) = the smallest m with c <= 2 (4^m - 1) / 3,
+// that is 3c < 2 4^m + 1; the recoding's 70 - cols(c) leading digits are zero.
+// An item's class is max(cols(|c0|), cols(c1)) clamped to kColNeedMin ..
+// kColNeedMax, numbered from the longest: class 0 needs >= 67 columns, class
+// kColClasses - 1 at most 62 (64: 52%, 65: 41% of random challenges).
+constexpr int kColNeedMin = 62, kColNeedMax = 67, kColClasses = kColNeedMax - kColNeedMin + 1;
+// limb j of 2 (4^m - 1) / 3, chunks 0b10
+HSV_INL constexpr uint32_t col_reach_limb(int m, int j) { return col_const_limb(m, j) << 1; }
+HSV_INL uint32_t col_class(const uint32_t c0[5], const uint32_t c1[5]) {
+  uint32_t over = 0;  // thresholds below max(c0, c1)
+  HSV_UNROLL
+  for (int m = kColNeedMin; m < kColNeedMax; ++m) {
+    const uint32_t t[5] = {col_reach_limb(m, 0), col_reach_limb(m, 1), col_reach_limb(m, 2), col_reach_limb(m, 3),
+                           col_reach_limb(m, 4)};
+    over += (mp_lt<5>(t, c0) || mp_lt<5>(t, c1)) ? 1u : 0u;
+  }
+  return (uint32_t)(kColClasses - 1) - over;
+}
+
 template <int WA, class Put = PutPlain, bool KREC = false, int DW = WA>
 HSV_INL bool prep_from_hash(const uint32_t h[16], const uint32_t s[8], uint32_t *rec, uint64_t stride,
-                            int lat_bits = kLatCombBits, bool skip = false) {
+                            int lat_bits = kLatCombBits, bool skip = false, uint32_t *need = nullptr) {
   using G = HalfCombWindows<DW>;
+  static_assert(DW != 2 || WA != 2, "DW = 2 is the column format; straus_vt's 2-bit windows are not built");
   const uint32_t s_ok = sc_is_canonical(s);
   const sc k = sc_reduce512(h);
   const LatOut lat = lattice_reduce(k, lat_bits);
+  if constexpr (DW == 2) {
+    if (need) *need = col_class(lat.c0, lat.c1);
+  }
   uint32_t d[5];
-  recode_top5<DW, G::NW>(lat.c1, d);
+  if constexpr (DW == 2) recode_cols<G::NW>(lat.c1, d);
+  else recode_top5<DW, G::NW>(lat.c1, d);
   HSV_UNROLL
   for (int i = 0; i < 5; ++i) Put::u32(rec + i * stride, d[i]);
-  recode_top5<DW, G::NW>(lat.c0, d);
+  if constexpr (DW == 2) recode_cols<G::NW>(lat.c0, d);
+  else recode_top5<DW, G::NW>(lat.c0, d);
   HSV_UNROLL
   for (int i = 0; i < 5; ++i) Put::u32(rec + (5 + i) * stride, d[i]);
   const sc b = sc_mul_small(lat.c1, s);
@@ -292,10 +348,10 @@ HSV_INL bool prep_from_hash(const uint32_t h[16], const uint32_t s[8], uint32_t 
 
 template <int WA, class Put = PutPlain, int DW = WA>
 HSV_INL bool prep_scalars(const uint32_t pk[8], const uint32_t sig[16], const uint32_t msg[8], uint32_t *rec,
-                          uint64_t stride, int lat_bits = kLatCombBits) {
+                          uint64_t stride, int lat_bits = kLatCombBits, uint32_t *need = nullptr) {
   uint32_t h[16];
   sha512_96(sig, pk, msg, h);
-  return prep_from_hash<WA, Put, false, DW>(h, sig + 8, rec, stride, lat_bits);
+  return prep_from_hash<WA, Put, false, DW>(h, sig + 8, rec, stride, lat_bits, false, need);
 }
 
 // Point pass of a prepped item: the half-size equation of
@@ -321,6 +377,7 @@ HSV_INL bool prep_scalars(const uint32_t pk[8], const uint32_t sig[16], const ui
 // 2 bits from ONE table, where straus_vt spends two per 4 bits from two.  The
 // doublings and additions per bit are the same; the table is 12 lines instead
 // of 16 and costs 2 doublings + 8 additions to build instead of 2 + 12.
+// The record's digits are i in {-1 .. 2} and, after the flip, j in {-2 .. 2}.
 // Folded by sign, i in {0, 1, 2} and j in {-2 .. 2} (i = 0: j >= 0): with
 // s = 5i + j the line is |s| and the fold is s < 0, since |j| <= 2 < 5 --
 //   0 the identity (the shared line), 1, 2 = Q, 2Q, 5i + j the lines with P
@@ -337,10 +394,15 @@ HSV_INL uint32_t joint_line(int i, int j, uint32_t &neg) {
 }
 
 // a column's line and fold from the two scalars' 2-bit chunks (digit =
-// chunk - 2); flip: c0 < 0, the digit of |c0| changes sign
+// chunk - OFF); flip: c0 < 0, the digit of |c0| changes sign.  OFF =
+// kColOffset is the record's format: i = -1 folds to the lines 3 .. 7
+// (s = -5 + j < 0) and i = -2 does not occur.  OFF = 2 is the symmetric set of
+// recode_top5<2>; the table serves both.
+template <int OFF = 2>
 HSV_INL uint32_t joint_column(uint32_t ci, uint32_t cj, uint32_t flip, uint32_t &neg) {
-  const int j = (int)cj - 2;
-  return joint_line((int)ci - 2, flip ? -j : j, neg);
+  static_assert(OFF == 1 || OFF == 2, "digits in {-1 .. 2} or {-2 .. 1}");
+  const int j = (int)cj - OFF;
+  return joint_line((int)ci - OFF, flip ? -j : j, neg);
 }
 
 template <class VT>
@@ -400,7 +462,8 @@ HSV_INL void jt_build(VT &vt, const fe &xp, const fe &yp, const fe &xq, const fe
 }
 
 // Straus over the joint table: d[0] the digits of c1, d[1] those of |c0| (five
-// words each, NW 2-bit columns, the top column at the top bit); flip: c0 < 0.
+// words each, NW 2-bit columns of recode_cols, the top column at the top bit);
+// flip: c0 < 0.
 // Per column two doublings and one cached addition of +-line; T only where
 // the addition follows, and after the last column (the comb phase follows).
 // Leading columns that are zero in every lane of the wave are skipped, as in
@@ -414,7 +477,7 @@ HSV_INL ge_ext straus_joint(uint32_t d[2][5], VT &vt, uint32_t flip) {
   int top = NW - 1;
   HSV_NOUNROLL
   while (top > 0) {
-    const uint32_t nz = ((d[0][4] >> 30) ^ 2u) | ((d[1][4] >> 30) ^ 2u);
+    const uint32_t nz = ((d[0][4] >> 30) ^ (uint32_t)kColOffset) | ((d[1][4] >> 30) ^ (uint32_t)kColOffset);
     if (wave_any(nz)) break;
     limbs_shl<5>(d[0], 2);
     limbs_shl<5>(d[1], 2);
@@ -423,7 +486,7 @@ HSV_INL ge_ext straus_joint(uint32_t d[2][5], VT &vt, uint32_t flip) {
   HSV_NOUNROLL
   for (int c = top; c >= 0; --c) {
     uint32_t neg;
-    const uint32_t line = joint_column(d[0][4] >> 30, d[1][4] >> 30, flip, neg);
+    const uint32_t line = joint_column<kColOffset>(d[0][4] >> 30, d[1][4] >> 30, flip, neg);
     limbs_shl<5>(d[0], 2);
     limbs_shl<5>(d[1], 2);
     if (c != top) {

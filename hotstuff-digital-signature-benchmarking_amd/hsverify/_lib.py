@@ -31,7 +31,8 @@ HOOKS = ("hsv_test_inject_fault", "hsv_test_inject_mode", "hsv_test_corrupt_auto
          "hsv_test_pipe_schedule", "hsv_test_numa_plan", "hsv_test_pinned_thread_cpus", "hsv_test_signer_group",
          "hsv_test_tx_sign_chunk", "hsv_test_msg_sign_chunk", "hsv_test_stage_bytes", "hsv_test_committee_tx_counts",
          "hsv_test_committee_msgs_counts", "hsv_test_msgs_small", "hsv_test_msgs_form_counts",
-         "hsv_test_field_ops", "hsv_test_scalar_ops", "hsv_test_cmsg_indexed_form", "hsv_test_cmsg_indexed_counts")
+         "hsv_test_field_ops", "hsv_test_scalar_ops", "hsv_test_cmsg_indexed_form", "hsv_test_cmsg_indexed_counts",
+         "hsv_test_deal", "hsv_test_deal_counts")
 
 # flag bits (include/hsv.h)
 STRICT_OK = 0x01
@@ -181,6 +182,8 @@ def _declare(lib):
         "hsv_test_stage_bytes": (sz, [sz]),
         "hsv_test_msgs_small": (ctypes.c_int, [ctypes.c_int]),
         "hsv_test_msgs_form_counts": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64)]),
+        "hsv_test_deal": (ctypes.c_int, [ctypes.c_int]),
+        "hsv_test_deal_counts": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32)]),
     }
     # hooks (libhsv_test.so only) and entry points absent from older A/B builds (tools/ab_probe.py)
     optional = set(HOOKS) | {"hsv_host_call_stats", "hsv_host_call_marks", "hsv_pack_threads", "hsv_device_faults",

@@ -44,6 +44,28 @@ def set_lattice_bits(bits: int) -> int:
     return prev
 
 
+DEAL_ON = 1      # point-pass batches dealt by column count (the default)
+DEAL_COUNTS = 2  # each launch keeps its class-list lengths (deal_counts)
+
+
+def set_deal(mode: int) -> int:
+    """How the calling thread's following two-launch point passes take their
+    batches (hsv_test_deal): DEAL_ON dealt by column count, 0 index order;
+    | DEAL_COUNTS keeps each launch's class counts.  Returns the previous mode."""
+    prev = _lib.hook("hsv_test_deal")(int(mode))
+    if prev < 0:
+        raise ValueError(f"unknown dealing mode {mode}")
+    return prev
+
+
+def deal_counts() -> list:
+    """Items per column class of the calling thread's last launch under
+    DEAL_COUNTS: [needs >= 67 columns, 66, 65, 64, 63, <= 62]."""
+    out = (ctypes.c_uint32 * 6)()
+    _lib.check(_lib.hook("hsv_test_deal_counts")(out), "hsv_test_deal_counts")
+    return [int(x) for x in out]
+
+
 def inject_fault(mode: int) -> int:
     """Corrupt what the calling thread's following launches read back
     (INJECT_*; 0 = off; other threads are unaffected).  Returns the previous mode."""
