@@ -526,6 +526,29 @@ int committee_msgs_indexed_host(const hsv_committee &cm, const uint32_t *key_idx
 
 }  // namespace
 
+// The committee routes of the serialized-batch calls (hsv_batch_api.cpp), which
+// cannot see into the handle: its device, and committee_tx_enqueue over a span
+// table (n transactions in HBM, transaction i = d_bufs[d_spans[2i], d_spans[2i+1]),
+// rounds of kChunk in order on `s`, every flag byte written; device c current).
+int committee_device_of(const hsv_committee *cm) { return cm->dev.device; }
+
+int committee_tx_spans_enqueue(const hsv_committee *cm, DevCtx &c, const uint32_t *btable, const uint32_t *comb16,
+                               const uint8_t *d_bufs, const uint64_t *d_spans, size_t n, uint8_t *d_flags,
+                               uint32_t *d_fault, hipStream_t s) {
+  uint64_t *d_totals = nullptr;
+  const int rc = tx_counts_begin(c, s, &d_totals);
+  if (rc != HSV_OK) return rc;
+  for (size_t base = 0; base < n; base += kChunk) {
+    const size_t m = std::min(kChunk, n - base);
+    const hipError_t e = hsv_launch_committee_tx_spans(
+        d_bufs, d_spans + 2 * base, (uint32_t)m, cm->d_keytab, cm->keymask, KeyHash::seed(), cm->dev.d_pks,
+        cm->dev.d_kflags, cm->dev.n, cm->dev.d_tabptr, cm->dev.digit_bits, btable, comb16, d_flags + base, nullptr,
+        d_fault, d_totals, s);
+    if (e != hipSuccess) return hip_fail("committee transaction launch", e);
+  }
+  return HSV_OK;
+}
+
 int committee_tx_counts(uint64_t out[3]) {
   return counts_read(t_tx_counts, kTxCountOff, "no committee transaction call on this thread", out);
 }

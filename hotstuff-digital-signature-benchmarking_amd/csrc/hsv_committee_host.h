@@ -31,6 +31,16 @@ int committee_run(const CommitteeDev &cd, const uint32_t *key_idx, const uint8_t
 hipError_t build_tables(const uint8_t *d_encs, uint32_t nkeys, uint32_t *const *tables, uint8_t *d_kflags,
                         uint32_t *d_tmp, uint32_t tmp_keys, hipStream_t st, int digit_bits = 8);
 
+// The committee routes of the serialized-batch calls (hsv_batch_api.cpp): the
+// handle's device, and the rounds of hsv_committee_verify_transactions_device
+// over a span table (transaction i = d_bufs[d_spans[2i], d_spans[2i+1]); every
+// flag byte of the n transactions is written; device c current, its two B
+// tables ensured by the caller).
+int committee_device_of(const hsv_committee *cm);
+int committee_tx_spans_enqueue(const hsv_committee *cm, DevCtx &c, const uint32_t *btable, const uint32_t *comb16,
+                               const uint8_t *d_bufs, const uint64_t *d_spans, size_t n, uint8_t *d_flags,
+                               uint32_t *d_fault, hipStream_t s);
+
 // ---- hsv_resident.cpp --------------------------------------------------------------
 constexpr int kResidentUnavailable = 1;
 // One request of at most hsv_comb_resident_votes() votes: HSV_OK, an error

@@ -373,6 +373,11 @@ int batch_verdict(const uint8_t *flags, size_t n);
 // HSV_ERR_INVALID_ARG naming the first transaction shorter than 96 bytes.
 int tx_lengths_ok(const uint64_t *offsets, size_t tx_size, size_t n);
 
+// measurement hook (hsv_test_batch_stages, hsv_batch_api.cpp): the stages of
+// the generic serialized-batch device form between device events
+int batch_stage_times(const uint8_t *d_bufs, const uint64_t *d_offsets, size_t n_batches, size_t tx_cap,
+                      hsv_batch_result *d_results, float ms_out[4]);
+
 // ---- the staged host forms and the argument checks of the generic calls and
 // ---- their committee twins (hsv_tx.cpp, hsv_msgs_api.cpp) ----------------------
 // A step run once on the slot's stream after slot_prepare (the committee's

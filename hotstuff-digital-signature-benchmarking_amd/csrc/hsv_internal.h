@@ -338,6 +338,42 @@ int hsvi_cmsg_indexed_counts(uint64_t out[3]);
 // flags 0 (and STRICT_OK bit cleared) for transactions shorter than 96 bytes
 hipError_t hsv_launch_tx_mask(const uint64_t *offsets, uint32_t n, uint8_t *flags, uint32_t *strict_bits,
                               hipStream_t stream);
+// Span-table addressing (the serialized batches of hsv_batches_verify_bincode*):
+// transaction i is txs[spans[2i], spans[2i+1]), pairs of any order and distance;
+// a pair shorter than 96 bytes or decreasing is a malformed transaction, as
+// above.  hsv_launch_tx_records, hsv_launch_tx_mask and hsv_launch_committee_tx
+// over such a table: the span instantiations of the same kernels.
+hipError_t hsv_launch_tx_records_spans(const uint8_t *txs, const uint64_t *spans, uint32_t n, uint8_t *records,
+                                       hipStream_t stream);
+hipError_t hsv_launch_tx_mask_spans(const uint64_t *spans, uint32_t n, uint8_t *flags, uint32_t *strict_bits,
+                                    hipStream_t stream);
+hipError_t hsv_launch_committee_tx_spans(const uint8_t *txs, const uint64_t *spans, uint32_t n,
+                                         const uint32_t *keytab, uint32_t keymask, uint64_t seed, const uint8_t *pks,
+                                         const uint8_t *key_flags, uint32_t nkeys, const uint32_t *const *key_tables,
+                                         int digit_bits, const uint32_t *btable, const uint32_t *comb16,
+                                         uint8_t *flags_out, uint32_t *strict_bits, uint32_t *fault, uint64_t *totals,
+                                         hipStream_t stream);
+
+// ---- serialized mempool batches (hsv_batchwire.hip) -------------------------
+// The device-side parse of n_batches bincode MempoolMessage::Batch messages,
+// batch b = bufs[offsets[b], offsets[b+1]) at any alignment (hsv_batchscan.hpp).
+// Four launches on `stream`, all sized by n_batches:
+//   count   one wave per batch: status[b] (kBatchOk / kBatchParse) and count[b]
+//           (0 for a malformed batch);
+//   index   first[b] = the counts before b, first[n_batches] = their sum; a batch
+//           with first[b] + count[b] > tx_cap becomes kBatchOverflow;
+//   spans   one wave per kBatchOk batch writes its transactions' span pairs,
+//           relative to bufs, at spans[2 * first[b] ..] (the caller zeroed
+//           spans[0 .. 2 * tx_cap), so every other entry reads as an empty span).
+// hsv_launch_batch_reduce (after the verification): results[b] = {status, index,
+// n_tx, first} from status / count / first and the flags of its transactions
+// (kBatchTx and the lowest index whose flags lack HSV_STRICT_OK).  results is a
+// hsv_batch_result array (include/hsv.h).
+hipError_t hsv_launch_batch_scan(const uint8_t *bufs, const uint64_t *offsets, uint32_t n_batches, uint64_t tx_cap,
+                                 uint32_t *status, uint64_t *count, uint64_t *first, uint64_t *spans,
+                                 hipStream_t stream);
+hipError_t hsv_launch_batch_reduce(const uint32_t *status, const uint64_t *count, const uint64_t *first,
+                                   const uint8_t *flags, uint32_t n_batches, void *results, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -46,9 +46,16 @@ constexpr int kTxBlock = 256;
 // offsets is given, else i*tx_size, (i+1)*tx_size.  A transaction shorter
 // than 96 bytes (the reference's slice would panic) gets an all-zero record
 // here and flags 0 from hsv_tx_mask_kernel.
+// SPANS (the serialized batches of hsv_batches_verify_bincode*, whose
+// transactions are separated by length prefixes and batch headers): offsets
+// is a span table, transaction i is [offsets[2i], offsets[2i+1]).
+template <bool SPANS = false>
 __device__ __forceinline__ bool tx_span(const uint64_t *offsets, uint64_t tx_size, uint32_t i, uint64_t &lo,
                                         uint64_t &hi) {
-  if (offsets) {
+  if constexpr (SPANS) {
+    lo = offsets[2ull * i];
+    hi = offsets[2ull * i + 1];
+  } else if (offsets) {
     lo = offsets[i];
     hi = offsets[i + 1];
   } else {
@@ -96,11 +103,12 @@ struct PutWriteThrough {
 // well-formed.  Every lane of the wave calls this: the wave's loads are
 // cooperative (tx_stage_chunks), each lane loops over its own blocks, the wave
 // over its longest message.
+template <bool SPANS = false>
 __device__ __forceinline__ bool tx_record_words(const uint8_t *__restrict__ txs, const uint64_t *__restrict__ offsets,
                                                 uint64_t tx_size, uint32_t n, uint32_t i, uint32_t lane,
                                                 uint4 *stage, uint32_t r[32]) {
   uint64_t lo = 0, hi = 0;
-  const bool ok = i < n && tx_span(offsets, tx_size, i, lo, hi);
+  const bool ok = i < n && tx_span<SPANS>(offsets, tx_size, i, lo, hi);
   const uintptr_t base = reinterpret_cast<uintptr_t>(txs);
   const uint4 *q = reinterpret_cast<const uint4 *>(base & ~uintptr_t(15));
   const uint64_t start = (uint64_t)(base & 15u) + lo;
@@ -162,7 +170,7 @@ __device__ __forceinline__ bool tx_record_words(const uint8_t *__restrict__ txs,
 // n - 1 and stores the same bytes again, so no store sits in a lane-dependent
 // region -- nested conditional stores inside the loop made hipcc compile the
 // loop's back edge divergent (the round-1 hang pattern, tests/test_kernel_isa.py).
-template <bool PREP, bool CLAMP, class Rec, class Put>
+template <bool PREP, bool CLAMP, class Rec, class Put, bool SPANS = false>
 __device__ __forceinline__ void tx_record_lane(const uint8_t *__restrict__ txs, const uint64_t *__restrict__ offsets,
                                                uint64_t tx_size, uint32_t n, uint32_t i_in, uint32_t lane,
                                                uint4 *stage, const Rec &out, uint32_t *__restrict__ prep,
@@ -170,7 +178,7 @@ __device__ __forceinline__ void tx_record_lane(const uint8_t *__restrict__ txs, 
                                                int lat_bits) {
   const uint32_t i = CLAMP && i_in >= n ? n - 1u : i_in;
   uint32_t r[32];
-  (void)tx_record_words(txs, offsets, tx_size, n, i, lane, stage, r);
+  (void)tx_record_words<SPANS>(txs, offsets, tx_size, n, i, lane, stage, r);
   if (CLAMP || i < n) {
     HSV_UNROLL
     for (int j = 0; j < 8; ++j) out.put(i, j, r);
@@ -183,8 +191,8 @@ __device__ __forceinline__ void tx_record_lane(const uint8_t *__restrict__ txs, 
 }
 
 // The record kernels: one lane per transaction (PREP: with the prepass; the
-// point pass is the next launch on the stream).
-template <bool PREP>
+// point pass is the next launch on the stream).  SPANS: tx_span's span table.
+template <bool PREP, bool SPANS = false>
 __global__ void __launch_bounds__(kTxBlock) hsv_tx_record_kernel(const uint8_t *__restrict__ txs,
                                                                   const uint64_t *__restrict__ offsets,
                                                                   uint64_t tx_size, uint32_t n,
@@ -196,7 +204,7 @@ __global__ void __launch_bounds__(kTxBlock) hsv_tx_record_kernel(const uint8_t *
   if constexpr (PREP) __builtin_amdgcn_s_setprio(3);  // as hsv_prep_kernel: ahead of a running point pass
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
   if (blockIdx.x * kTxBlock + wv * 64u >= n) return;  // whole wave past the end
-  tx_record_lane<PREP, false, TxRecPlain, PutPlain>(txs, offsets, tx_size, n, blockIdx.x * kTxBlock + threadIdx.x, lane,
+  tx_record_lane<PREP, false, TxRecPlain, PutPlain, SPANS>(txs, offsets, tx_size, n, blockIdx.x * kTxBlock + threadIdx.x, lane,
                                              stage_all[wv], TxRecPlain{rec}, prep, fb_count, fb_list, lat_bits);
 }
 
@@ -340,12 +348,13 @@ hsv_verify_tx_fused_kernel(const uint8_t *__restrict__ txs, const uint64_t *__re
 }
 
 // Zero the flags (and the STRICT_OK bit) of transactions shorter than 96 bytes.
+template <bool SPANS>
 __global__ void __launch_bounds__(kTxBlock) hsv_tx_mask_kernel(const uint64_t *__restrict__ offsets, uint32_t n,
                                                                 uint8_t *flags, uint32_t *strict_bits) {
   const uint32_t i = blockIdx.x * kTxBlock + threadIdx.x;
   if (i >= n) return;
   uint64_t lo, hi;
-  if (tx_span(offsets, 0, i, lo, hi)) return;
+  if (tx_span<SPANS>(offsets, 0, i, lo, hi)) return;
   if (flags) flags[i] = 0;
   if (strict_bits) atomicAnd(strict_bits + (i >> 5), ~(1u << (i & 31u)));
 }
@@ -372,6 +381,7 @@ __global__ void __launch_bounds__(kTxBlock) hsv_tx_mask_kernel(const uint64_t *_
 // hit means the 32 pk bytes equal the member's.
 // The passes' and the list compaction's rules: hsv_routed.hpp.
 // One lane per transaction, so no loop surrounds the list stores.
+template <bool SPANS>
 __global__ void __launch_bounds__(kTxBlock)
 hsv_ctx_route_kernel(const uint8_t *__restrict__ txs, const uint64_t *__restrict__ offsets, uint64_t tx_size, uint32_t n,
                      uint4 *__restrict__ rec, const uint32_t *__restrict__ keytab, uint32_t keymask, uint64_t seed,
@@ -384,7 +394,7 @@ hsv_ctx_route_kernel(const uint8_t *__restrict__ txs, const uint64_t *__restrict
   if (blockIdx.x * kTxBlock + wv * 64u >= n) return;  // whole wave past the end
   const uint32_t i = blockIdx.x * kTxBlock + threadIdx.x;
   uint32_t r[32];
-  const bool ok = tx_record_words(txs, offsets, tx_size, n, i, lane, stage_all[wv], r);
+  const bool ok = tx_record_words<SPANS>(txs, offsets, tx_size, n, i, lane, stage_all[wv], r);
   if (i < n) {
     const TxRecPlain out{rec};
     HSV_UNROLL
@@ -576,7 +586,29 @@ extern "C" hipError_t hsv_launch_tx_mask(const uint64_t *offsets, uint32_t n, ui
                                          uint32_t *strict_bits, hipStream_t stream) {
   if (n == 0 || !offsets) return hipSuccess;
   const uint32_t grid = (n + hsv::kTxBlock - 1) / hsv::kTxBlock;
-  hipLaunchKernelGGL(hsv::hsv_tx_mask_kernel, dim3(grid), dim3(hsv::kTxBlock), 0, stream, offsets, n, flags,
+  hipLaunchKernelGGL(hsv::hsv_tx_mask_kernel<false>, dim3(grid), dim3(hsv::kTxBlock), 0, stream, offsets, n, flags,
+                     strict_bits);
+  return hipGetLastError();
+}
+
+// The two launches above for a span table (hsv_internal.h): transaction i is
+// txs[spans[2i], spans[2i+1]).
+extern "C" hipError_t hsv_launch_tx_records_spans(const uint8_t *txs, const uint64_t *spans, uint32_t n,
+                                                  uint8_t *records, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  if (!spans) return hipErrorInvalidValue;
+  const uint32_t grid = (n + hsv::kTxBlock - 1) / hsv::kTxBlock;
+  hipLaunchKernelGGL((hsv::hsv_tx_record_kernel<false, true>), dim3(grid), dim3(hsv::kTxBlock), 0, stream, txs, spans,
+                     (uint64_t)0, n, reinterpret_cast<uint4 *>(records), nullptr, nullptr, nullptr, 0);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t hsv_launch_tx_mask_spans(const uint64_t *spans, uint32_t n, uint8_t *flags,
+                                               uint32_t *strict_bits, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  if (!spans) return hipErrorInvalidValue;
+  const uint32_t grid = (n + hsv::kTxBlock - 1) / hsv::kTxBlock;
+  hipLaunchKernelGGL(hsv::hsv_tx_mask_kernel<true>, dim3(grid), dim3(hsv::kTxBlock), 0, stream, spans, n, flags,
                      strict_bits);
   return hipGetLastError();
 }
@@ -618,14 +650,14 @@ extern "C" hipError_t hsv_launch_tx_fused(uint32_t grid, const uint8_t *txs, con
 // n <= 2^22 transactions: the round of hsv_routed.hpp (RoutedRound: grids,
 // memsets, the comb pass by table width).  Workspace from the library pool:
 // per-lane tables | counters | canaries | records | hit list | miss list |
-// fallback list | prepass words.
-extern "C" hipError_t hsv_launch_committee_tx(const uint8_t *txs, const uint64_t *offsets, uint64_t tx_size, uint32_t n,
-                                              const uint32_t *keytab, uint32_t keymask, uint64_t seed,
-                                              const uint8_t *pks, const uint8_t *key_flags, uint32_t nkeys,
-                                              const uint32_t *const *key_tables, int digit_bits,
-                                              const uint32_t *btable, const uint32_t *comb16, uint8_t *flags_out,
-                                              uint32_t *strict_bits, uint32_t *fault, uint64_t *totals,
-                                              hipStream_t stream) {
+// fallback list | prepass words.  SPANS: offsets is tx_span's span table.
+namespace {
+template <bool SPANS>
+hipError_t launch_committee_tx(const uint8_t *txs, const uint64_t *offsets, uint64_t tx_size, uint32_t n,
+                               const uint32_t *keytab, uint32_t keymask, uint64_t seed, const uint8_t *pks,
+                               const uint8_t *key_flags, uint32_t nkeys, const uint32_t *const *key_tables,
+                               int digit_bits, const uint32_t *btable, const uint32_t *comb16, uint8_t *flags_out,
+                               uint32_t *strict_bits, uint32_t *fault, uint64_t *totals, hipStream_t stream) {
   if (n == 0) return hipSuccess;
   if (n > (1u << 22) || (digit_bits != 8 && digit_bits != 4) || !btable || !comb16 || !fault || (nkeys && (!keytab || !pks || !key_flags || !key_tables)))
     return hipErrorInvalidValue;
@@ -651,7 +683,7 @@ extern "C" hipError_t hsv_launch_committee_tx(const uint8_t *txs, const uint64_t
   const uint32_t inject = (uint32_t)hsvi_inject_mode();
   e = hsv::RoutedRound::zero(ctr, strict_bits, n, stream);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(hsv::hsv_ctx_route_kernel, dim3(r.blocks_needed), dim3(hsv::kTxBlock), 0, stream, txs, offsets,
+    hipLaunchKernelGGL(hsv::hsv_ctx_route_kernel<SPANS>, dim3(r.blocks_needed), dim3(hsv::kTxBlock), 0, stream, txs, offsets,
                        tx_size, n, reinterpret_cast<uint4 *>(records), keytab, keymask, seed, pks, nkeys, ctr, hit_list,
                        miss_list, prep, fb_list, hsvi_lattice_bits(), flags_out);
     e = hipGetLastError();
@@ -669,4 +701,28 @@ extern "C" hipError_t hsv_launch_committee_tx(const uint8_t *txs, const uint64_t
     e = hipGetLastError();
   }
   return ws.done(e);
+}
+}  // namespace
+
+extern "C" hipError_t hsv_launch_committee_tx(const uint8_t *txs, const uint64_t *offsets, uint64_t tx_size, uint32_t n,
+                                              const uint32_t *keytab, uint32_t keymask, uint64_t seed,
+                                              const uint8_t *pks, const uint8_t *key_flags, uint32_t nkeys,
+                                              const uint32_t *const *key_tables, int digit_bits,
+                                              const uint32_t *btable, const uint32_t *comb16, uint8_t *flags_out,
+                                              uint32_t *strict_bits, uint32_t *fault, uint64_t *totals,
+                                              hipStream_t stream) {
+  return launch_committee_tx<false>(txs, offsets, tx_size, n, keytab, keymask, seed, pks, key_flags, nkeys, key_tables,
+                                    digit_bits, btable, comb16, flags_out, strict_bits, fault, totals, stream);
+}
+
+extern "C" hipError_t hsv_launch_committee_tx_spans(const uint8_t *txs, const uint64_t *spans, uint32_t n,
+                                                    const uint32_t *keytab, uint32_t keymask, uint64_t seed,
+                                                    const uint8_t *pks, const uint8_t *key_flags, uint32_t nkeys,
+                                                    const uint32_t *const *key_tables, int digit_bits,
+                                                    const uint32_t *btable, const uint32_t *comb16,
+                                                    uint8_t *flags_out, uint32_t *strict_bits, uint32_t *fault,
+                                                    uint64_t *totals, hipStream_t stream) {
+  if (n && !spans) return hipErrorInvalidValue;
+  return launch_committee_tx<true>(txs, spans, 0, n, keytab, keymask, seed, pks, key_flags, nkeys, key_tables,
+                                   digit_bits, btable, comb16, flags_out, strict_bits, fault, totals, stream);
 }

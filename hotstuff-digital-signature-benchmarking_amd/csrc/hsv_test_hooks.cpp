@@ -91,6 +91,11 @@ int hsv_test_cmsg_indexed_counts(uint64_t out[3]) {
   if (!out) return HSV_ERR_INVALID_ARG;
   return hsvi_cmsg_indexed_counts(out) == 0 ? HSV_OK : HSV_ERR_HIP;
 }
+int hsv_test_batch_stages(const uint8_t *d_bufs, const uint64_t *d_offsets, size_t n_batches, size_t tx_cap,
+                          void *d_results, float ms_out[4]) {
+  return hsvh::batch_stage_times(d_bufs, d_offsets, n_batches, tx_cap, static_cast<hsv_batch_result *>(d_results),
+                                 ms_out);
+}
 size_t hsv_test_stage_bytes(size_t bytes) { return hsvh::g_stage_bytes.exchange(bytes ? bytes : hsvh::kStageBytes); }
 
 }  // extern "C"

@@ -150,6 +150,15 @@ HSV_API int hsv_test_cmsg_indexed_form(int mode);
  * on their hit lists (counted on the current device: valid once the caller has
  * synchronised its streams).  HSV_OK, or HSV_ERR_HIP. */
 HSV_API int hsv_test_cmsg_indexed_counts(uint64_t out[3]);
+/* Measurement only (tools/batch_wire_probe.py): the stages of the generic
+ * route of hsv_batches_verify_bincode_device, one after the other on the null
+ * stream of the buffers' device, each between two device events: ms_out[0] the
+ * parse (count, index and span kernels), [1] the span-mode record kernel, [2]
+ * the verification launch over the records and the mask, [3] the verdict
+ * kernel.  n_batches >= 1, 1 <= tx_cap <= 2^22; d_results as that call's.
+ * Synchronises.  HSV_OK or an error. */
+HSV_API int hsv_test_batch_stages(const uint8_t *d_bufs, const uint64_t *d_offsets, size_t n_batches, size_t tx_cap,
+                                  void *d_results, float ms_out[4]);
 
 #ifdef __cplusplus
 }

@@ -401,4 +401,52 @@ bool parse_vote(const uint8_t *buf, size_t len, VoteParsed &out, std::string &er
   return true;
 }
 
+bool parse_batch(const uint8_t *buf, size_t len, uint64_t base, std::vector<uint64_t> *spans, size_t &n_tx,
+                 std::string &err) {
+  n_tx = 0;
+  if (!buf && len) {
+    err = "null buffer";
+    return false;
+  }
+  Reader r{buf, len};
+  const uint8_t *tag = nullptr;
+  uint64_t count = 0;
+  if (!r.bytes(tag, 4) || !r.u64(count)) {
+    err = "truncated batch header";
+    return false;
+  }
+  if (tag[0] | tag[1] | tag[2] | tag[3]) {
+    err = "not a MempoolMessage::Batch (variant tag is not 0)";
+    return false;
+  }
+  if (count > r.left / 8) {  // a transaction is at least its 8-byte length
+    err = "transaction count exceeds the buffer";
+    return false;
+  }
+  const size_t mark = spans ? spans->size() : 0;
+  if (spans) spans->reserve(mark + 2 * (size_t)count);
+  for (uint64_t i = 0; i < count; ++i) {
+    uint64_t n = 0;
+    const uint8_t *body = nullptr;
+    // (compared against the bytes left: no addition that could overflow)
+    if (!r.u64(n) || n > r.left || !r.bytes(body, (size_t)n)) {
+      if (spans) spans->resize(mark);
+      err = "transaction " + std::to_string(i) + ": truncated";
+      return false;
+    }
+    if (spans) {
+      const uint64_t lo = base + (uint64_t)(body - buf);
+      spans->push_back(lo);
+      spans->push_back(lo + n);
+    }
+  }
+  if (r.left != 0) {
+    if (spans) spans->resize(mark);
+    err = "trailing bytes after the batch";
+    return false;
+  }
+  n_tx = (size_t)count;
+  return true;
+}
+
 }  // namespace hsvw

@@ -64,6 +64,19 @@ bool parse_block(const uint8_t *buf, size_t len, BlockParsed &out, std::string &
 bool parse_timeout(const uint8_t *buf, size_t len, TimeoutParsed &out, std::string &err);
 bool parse_vote(const uint8_t *buf, size_t len, VoteParsed &out, std::string &err);
 
+// mempool::MempoolMessage::Batch(Vec<Vec<u8>>) as BatchMaker::seal serializes it
+// (mempool/src/batch_maker.rs:127-131) and Core::make_vote reads it back
+// (consensus/src/core.rs:113-142): u32 LE variant tag (0 = Batch) | u64 count |
+// count x (u64 length, bytes).  n_tx: the count; spans (optional): transaction
+// i is buf[s[2i] - base, s[2i+1] - base) for the 2 * n_tx entries s appended to
+// it (nothing is appended on failure).  Malformed: a tag other than 0 (a
+// BatchRequest is tag 1), truncation, a count above the remaining bytes / 8, a
+// length past the buffer's end, trailing bytes -- the rules of the device walk
+// (hsv_batchscan.hpp), which tests/native/batchscan_host.cpp holds against
+// this function.
+bool parse_batch(const uint8_t *buf, size_t len, uint64_t base, std::vector<uint64_t> *spans, size_t &n_tx,
+                 std::string &err);
+
 // base64 0.13 standard decoding (PublicKey::decode_base64, crypto/src/lib.rs:73-79)
 bool b64_decode(const uint8_t *s, size_t n, std::vector<uint8_t> &out);
 

@@ -118,3 +118,21 @@ def verify_batch_transactions(txs: Iterable[bytes], committee=None) -> bool:
         return True
     flags = committee.verify_transactions(txs) if committee is not None else verify_transactions(txs)
     return bool((flags & _lib.STRICT_OK).all())
+
+
+def verify_serialized_batch(buf: bytes, committee=None) -> bool:
+    """``Core::make_vote``'s check from the stored bytes (core.rs:113-142): the
+    bincode of ``MempoolMessage::Batch`` as read from the store, verified where
+    it lies (``hsv_batch_verify_bincode``; nothing is deserialized or
+    re-packed).  True iff it is a well-formed Batch and every transaction
+    verifies; False for a failing transaction (one shorter than 96 bytes
+    included) and for malformed bytes or a ``BatchRequest``, which make_vote
+    rejects alike.  ``committee`` as in :func:`filter_transactions`."""
+    from . import wire
+    try:
+        ok, _ = wire.batch_verify(buf, committee)
+    except _lib.HsvLibraryError as e:
+        if "HSV_ERR_PARSE" in str(e):
+            return False
+        raise
+    return ok

@@ -213,6 +213,109 @@ def blocks_verify(blocks: Sequence[bytes], committee=None):
     return rc, [results[i].as_tuple() for i in range(len(blocks))]
 
 
+# ---- serialized mempool batches (mempool/src/batch_maker.rs:127-131) -------------
+# hsv_batch_result.status (include/hsv.h)
+BATCH_OK, BATCH_TX, BATCH_PARSE, BATCH_OVERFLOW = range(4)
+
+
+class BatchResult(ctypes.Structure):
+    """hsv_batch_result: the batch's verdict, its lowest failing transaction,
+    its transaction count and its first index in the flags array."""
+    _fields_ = [("status", ctypes.c_uint32), ("index", ctypes.c_uint32), ("n_tx", ctypes.c_uint64),
+                ("first", ctypes.c_uint64)]
+
+    def as_tuple(self):
+        return int(self.status), int(self.index), int(self.n_tx), int(self.first)
+
+
+def encode_batch(txs: Sequence[bytes]) -> bytes:
+    """bincode of mempool::MempoolMessage::Batch(Vec<Vec<u8>>) as
+    BatchMaker::seal serializes it: u32 variant tag 0 | u64 count | count x
+    (u64 length, bytes)."""
+    out = [struct.pack("<IQ", 0, len(txs))]
+    for t in txs:
+        out.append(_str(bytes(t)))
+    return b"".join(out)
+
+
+def encode_batch_request(digests: Sequence[bytes], requestor: bytes) -> bytes:
+    """bincode of MempoolMessage::BatchRequest(Vec<Digest>, PublicKey): variant
+    tag 1 -- what Core::make_vote rejects where it expects a Batch."""
+    return struct.pack("<IQ", 1, len(digests)) + b"".join(bytes(d) for d in digests) + encode_public_key(requestor)
+
+
+def decode_batch(buf: bytes):
+    """``hsv_batch_parse_bincode`` (host only, no GPU) -> the transactions.
+    Raises HsvLibraryError (HSV_ERR_PARSE) on malformed bytes."""
+    lib = _lib.load()
+    buf = bytes(buf)
+    n = ctypes.c_size_t(0)
+    _lib.check(lib.hsv_batch_parse_bincode(buf, len(buf), ctypes.byref(n), None, 0), "hsv_batch_parse_bincode")
+    spans = np.zeros(2 * n.value, np.uint64)
+    _lib.check(lib.hsv_batch_parse_bincode(buf, len(buf), ctypes.byref(n), ctypes.c_void_p(spans.ctypes.data),
+                                           spans.size), "hsv_batch_parse_bincode")
+    return [buf[int(spans[2 * i]): int(spans[2 * i + 1])] for i in range(n.value)]
+
+
+def batches_verify(batches: Sequence[bytes], committee=None):
+    """Serialized batches in one call (``hsv_batches_verify_bincode``) ->
+    (number of batches that pass, [(status, index, n_tx, first)] per batch,
+    flag bytes of all transactions in batch order).  A batch that does not
+    parse gets BATCH_PARSE and leaves its neighbours alone."""
+    lib = _lib.load()
+    offsets = np.zeros(len(batches) + 1, np.uint64)
+    offsets[1:] = np.cumsum([len(b) for b in batches], dtype=np.uint64)
+    bufs = b"".join(bytes(b) for b in batches)
+    flags = np.zeros(max(1, len(bufs) // 8), np.uint8)  # a transaction is at least its 8-byte length
+    results = (BatchResult * max(1, len(batches)))()
+    rc = _lib.check(lib.hsv_batches_verify_bincode(_handle(committee), bufs, ctypes.c_void_p(offsets.ctypes.data),
+                                                   len(batches), ctypes.cast(results, ctypes.c_void_p),
+                                                   ctypes.c_void_p(flags.ctypes.data), flags.size),
+                    "hsv_batches_verify_bincode")
+    res = [results[i].as_tuple() for i in range(len(batches))]
+    total = sum(r[2] for r in res)
+    return rc, res, flags[:total]
+
+
+def batch_verify(buf: bytes, committee=None):
+    """One serialized batch (``hsv_batch_verify_bincode``) -> (ok, (status,
+    index, n_tx, first)).  Raises HsvLibraryError (HSV_ERR_PARSE) on malformed
+    bytes."""
+    lib = _lib.load()
+    buf = bytes(buf)
+    res = BatchResult()
+    rc = _lib.check(lib.hsv_batch_verify_bincode(_handle(committee), buf, len(buf), ctypes.byref(res)),
+                    "hsv_batch_verify_bincode")
+    return rc == 1, res.as_tuple()
+
+
+def batches_verify_device(bufs, offsets, n_batches: int, tx_cap: int, results, flags=None, committee=None,
+                          stream=None, fault=None) -> None:
+    """Enqueue ``hsv_batches_verify_bincode_device`` on device-resident bytes:
+    ``bufs`` a torch uint8 tensor, ``offsets`` an int64 tensor of n_batches + 1
+    byte offsets, ``results`` an int64 tensor of 3 * n_batches words (one
+    hsv_batch_result each; :func:`batch_results` reads them), ``flags``
+    (optional) a uint8 tensor of tx_cap bytes.  No synchronisation."""
+    from .verifier import _fault_ptr
+    import torch
+
+    if stream is None:
+        stream = torch.cuda.current_stream(bufs.device).cuda_stream
+    lib = _lib.load()
+    rc = lib.hsv_batches_verify_bincode_device(
+        _handle(committee), ctypes.c_void_p(bufs.data_ptr()), ctypes.c_void_p(offsets.data_ptr()), n_batches, tx_cap,
+        ctypes.c_void_p(results.data_ptr()), ctypes.c_void_p(flags.data_ptr()) if flags is not None else None,
+        _fault_ptr(fault), ctypes.c_void_p(stream))
+    _lib.check(rc, "hsv_batches_verify_bincode_device")
+
+
+def batch_results(words) -> list:
+    """[(status, index, n_tx, first)] from the 3 * n 64-bit words of n
+    hsv_batch_result structures (a numpy array or a CPU tensor)."""
+    w = np.asarray(words).astype(np.int64).view(np.uint64).reshape(-1, 3)
+    return [(int(a & np.uint64(0xffffffff)), int(a >> np.uint64(32)), int(n), int(f)) for a, n, f in w]
+
+
 def qc_verify(buf: bytes):
     """-> (ok: bool, decoded public keys (n, 32) u8).  Raises HsvLibraryError on
     malformed bytes (HSV_ERR_PARSE) or an infrastructure error."""

@@ -25,6 +25,9 @@
  *                                                                   hsv_blocks_verify_bincode,
  *                                                                   hsv_timeout_verify_bincode,
  *                                                                   hsv_vote_verify_bincode
+ *   Core::make_vote's payload check from the stored batch bytes
+ *                        consensus/src/core.rs:113-142          -> hsv_batch_verify_bincode,
+ *                                                                   hsv_batches_verify_bincode*
  *
  * Plain pointers and sizes only.  All inputs are borrowed for the duration of
  * the call; the library never retains a caller pointer.  Every entry point is
@@ -116,8 +119,8 @@ HSV_API const char *hsv_last_error(void);
  * hsv_verify_transactions_device) take the optional d_fault argument before
  * `stream`; a caller built against 0.2.x headers must be rebuilt (check
  * HSV_ABI_VERSION against hsv_abi_version() at startup).  Entry points added
- * since (the last: hsv_proposal_verify and the block, timeout and vote calls
- * around it) change no existing signature
+ * since (the last: the serialized-batch calls hsv_batch*_bincode*) change no
+ * existing signature
  * and leave both the version and HSV_ABI_VERSION as they are. */
 #define HSV_ABI_VERSION 3
 HSV_API const char *hsv_version(void);
@@ -597,6 +600,102 @@ HSV_API int hsv_vote_verify_bincode(hsv_committee *c, const uint8_t *buf, size_t
  * n_blocks == 0), or < 0 for an infrastructure error. */
 HSV_API int hsv_blocks_verify_bincode(hsv_committee *c, const uint8_t *bufs, const uint64_t *offsets,
                                       size_t n_blocks, hsv_proposal_result *results);
+
+/* ---- serialized mempool batches -------------------------------------------
+ * Core::make_vote's payload check (consensus/src/core.rs:113-142) from the
+ * stored bytes: a mempool::MempoolMessage::Batch(Vec<Vec<u8>>) as
+ * BatchMaker::seal serializes it (mempool/src/batch_maker.rs:127-131; bincode
+ * 1.3 defaults): u32 LE variant tag (0 = Batch) | u64 LE count | count x (u64 LE
+ * length, bytes).  The transactions are verified where they lie: nothing is
+ * deserialized, re-packed or copied on the device; the transaction kernels
+ * address them through a table of span pairs.
+ * Rule, per transaction: the flags of hsv_verify_transactions* for the same
+ * bytes, bit for bit (Signature::verify over SHA-512(message)[..32], the last
+ * 96 bytes pk || R || s).  A transaction shorter than 96 bytes gets flags 0
+ * and is a rejection at its index (the reference's slice would panic; batches
+ * are untrusted network bytes).  A batch passes iff every transaction has
+ * HSV_STRICT_OK; an empty batch passes.
+ * Malformed (HSV_BATCH_PARSE; HSV_ERR_PARSE from the single-batch calls): a tag
+ * other than 0 (a BatchRequest, which make_vote rejects, is tag 1), truncation
+ * anywhere, a count above the remaining bytes / 8, a length that runs past the
+ * batch's own end (whatever bytes follow it), trailing bytes after the last
+ * transaction.  (bincode::deserialize itself would accept trailing bytes; this
+ * library's parsers reject them in every object.)  A malformed batch leaves
+ * its neighbours alone.
+ * The batch's own digest (its store key) and the stake and quorum checks stay
+ * with the caller. */
+#define HSV_BATCH_OK 0u
+#define HSV_BATCH_TX 1u       /* transaction `index` is the lowest that fails */
+#define HSV_BATCH_PARSE 2u    /* not a well-formed MempoolMessage::Batch */
+#define HSV_BATCH_OVERFLOW 3u /* device form: its transactions do not fit tx_cap */
+typedef struct hsv_batch_result {
+  uint32_t status, index;
+  uint64_t n_tx;  /* the batch's transactions; 0 for a malformed batch */
+  uint64_t first; /* the index of its first transaction in the flags array */
+} hsv_batch_result;
+
+/* The parse alone, on the host; needs no GPU.  1 = well-formed (n_tx_out,
+ * optional: the count), HSV_ERR_PARSE otherwise.  spans_out (optional,
+ * spans_cap entries): transaction i is buf[spans_out[2i], spans_out[2i+1]);
+ * spans_cap < 2 * count is HSV_ERR_INVALID_ARG. */
+HSV_API int hsv_batch_parse_bincode(const uint8_t *buf, size_t len, size_t *n_tx_out, uint64_t *spans_out,
+                                    size_t spans_cap);
+
+/* Host form: batch b is bufs[offsets[b] .. offsets[b+1]) (n_batches + 1
+ * non-decreasing offsets, else HSV_ERR_INVALID_ARG), at any alignment.
+ * Synchronous, on the home device (c == NULL: the generic kernels) or the
+ * committee's (c != NULL: the routes of hsv_committee_verify_transactions*; a
+ * compact committee is accepted like a full one).  The host parses -- a
+ * malformed batch costs no device work -- and stages whole batches in rounds
+ * within the item and byte limits of hsv_verify_transactions (2^22
+ * transactions, 2^29 bytes); a single batch above the byte limit is
+ * HSV_ERR_INVALID_ARG (the reference's frames are far smaller).  Not sharded
+ * across devices.  Transactions are numbered in batch order over the
+ * well-formed batches; results (optional, n_batches entries) and flags_out
+ * (optional; flags_cap below the total is HSV_ERR_INVALID_ARG before any device
+ * work) as above.  Returns the number of batches with HSV_BATCH_OK, or < 0:
+ * HSV_ERR_NO_DEVICE without a GPU, HSV_ERR_DEVICE_FAULT for a failed
+ * self-check. */
+HSV_API int hsv_batches_verify_bincode(hsv_committee *c, const uint8_t *bufs, const uint64_t *offsets,
+                                       size_t n_batches, hsv_batch_result *results, uint8_t *flags_out,
+                                       size_t flags_cap);
+/* One batch: 1 = every transaction verifies, 0 = one does not (res says which),
+ * HSV_ERR_PARSE, other < 0.  res (optional) is written on 0 and 1 only. */
+HSV_API int hsv_batch_verify_bincode(hsv_committee *c, const uint8_t *buf, size_t len, hsv_batch_result *res);
+
+/* Device form: the batches already in HBM, parsed there (one wave per batch
+ * streams it through LDS; csrc/hsv_batchwire.hip).  Stream-ordered, never
+ * synchronises; d_fault (optional), device ownership and the stream checks as
+ * hsv_verify_transactions_device (c == NULL) / hsv_committee_verify_device.
+ * d_offsets: n_batches + 1 entries, 8-byte aligned; a batch whose offsets
+ * decrease is HSV_BATCH_PARSE.  d_results: n_batches entries, 8-byte aligned.
+ * d_flags (optional): every byte of d_flags[0 .. tx_cap) is written, bytes past
+ * the total are 0.  A batch whose transactions do not all lie below tx_cap gets
+ * HSV_BATCH_OVERFLOW and is not verified (n_tx and first still say what it
+ * needs); earlier batches are unaffected.  The transaction count is known on
+ * the device only, so every launch and the workspace (16 + 128 bytes per
+ * transaction, from the library's stream-ordered pool) are sized by tx_cap: the
+ * caller takes the exact count from hsv_batch_parse_bincode while the bytes
+ * pass through the host, or accepts the padding's cost -- a padded slot is
+ * verified like a malformed transaction.  tx_cap above 2^32 - 1 and n_batches
+ * above 2^32 - 1 are HSV_ERR_INVALID_ARG.
+ * When to use it (profiles/batch_wire_bench.json: 512-byte transactions, batches
+ * of 500,000 B = 977 transactions, p50, both sides in one run): for batches
+ * that already lie in HBM.  1024 batches take 10.23 ms against 9.47 ms of
+ * hsv_verify_transactions_device on the same transactions packed with
+ * precomputed offsets (1.08 x): the excess is the parse, 0.70 ms, which is one
+ * wave's serial walk per batch and so costs the same 0.63 - 0.70 ms for 1, 64 or
+ * 1024 batches.  It therefore dominates few batches: 64 take 1.50 against
+ * 0.98 ms (1.53 x), one takes 0.90 against 0.26 ms (3.4 x).  A caller whose
+ * bytes pass through the host takes the host form, where the parse costs
+ * nothing measurable: one batch of 500,000 B in 0.314 ms against 0.307 ms of
+ * hsv_verify_transactions on transactions already packed (15,000 B: 0.165
+ * against 0.163 ms), and the repacking that call needs (0.38 ms and 0.02 ms
+ * as a parse plus one copy per transaction) is saved. */
+HSV_API int hsv_batches_verify_bincode_device(const hsv_committee *c, const uint8_t *d_bufs,
+                                              const uint64_t *d_offsets, size_t n_batches, size_t tx_cap,
+                                              hsv_batch_result *d_results, uint8_t *d_flags, uint32_t *d_fault,
+                                              void *stream);
 
 /* ---- signing (host CPU; not on the hot path) ---------------------------- */
 /* Public key for a 32-byte secret seed (dalek Keypair from SecretKey). */

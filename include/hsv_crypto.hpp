@@ -716,4 +716,61 @@ class Committee {
 
 }  // namespace hsv
 
+// Core::make_vote's payload check from the stored bytes
+// (consensus/src/core.rs:113-142; hsv_batch*_verify_bincode, hsv.h): the bincode
+// of MempoolMessage::Batch(Vec<Vec<u8>>) verified where it lies.
+namespace mempool {
+
+// BatchMaker::seal's serialization (mempool/src/batch_maker.rs:127-131)
+inline std::vector<uint8_t> encode_batch(const std::vector<std::vector<uint8_t>> &txs) {
+  std::vector<uint8_t> out(12, 0);
+  auto put_u64 = [&](size_t at, uint64_t v) {
+    for (int i = 0; i < 8; ++i) out[at + i] = (uint8_t)(v >> (8 * i));
+  };
+  put_u64(4, txs.size());
+  for (const std::vector<uint8_t> &t : txs) {
+    out.resize(out.size() + 8);
+    put_u64(out.size() - 8, t.size());
+    out.insert(out.end(), t.begin(), t.end());
+  }
+  return out;
+}
+
+// True iff buf is a well-formed Batch whose transactions all verify; false for a
+// failing transaction (res, optional, says which) and for malformed bytes or a
+// BatchRequest, which make_vote rejects alike (res->status == HSV_BATCH_PARSE).
+// Infrastructure errors throw.  committee (optional): the known clients' keys.
+inline bool verify_serialized_batch(const uint8_t *buf, size_t len, hsv_committee *committee = nullptr,
+                                    hsv_batch_result *res = nullptr) {
+  hsv_batch_result r{};
+  const int rc = hsv_batch_verify_bincode(committee, buf, len, &r);
+  if (rc == HSV_ERR_PARSE) r.status = HSV_BATCH_PARSE;
+  else crypto::check_infra(rc, "hsv_batch_verify_bincode");
+  if (res) *res = r;
+  return rc == 1;
+}
+inline bool verify_serialized_batch(const std::vector<uint8_t> &buf, hsv_committee *committee = nullptr,
+                                    hsv_batch_result *res = nullptr) {
+  return verify_serialized_batch(buf.data(), buf.size(), committee, res);
+}
+
+// Several stored batches in one call (hsv_batches_verify_bincode): one verdict
+// per batch, a malformed one HSV_BATCH_PARSE.
+inline std::vector<hsv_batch_result> verify_serialized_batches(const std::vector<std::vector<uint8_t>> &batches,
+                                                               hsv_committee *committee = nullptr) {
+  std::vector<uint8_t> bufs;
+  std::vector<uint64_t> offsets(batches.size() + 1, 0);
+  for (size_t i = 0; i < batches.size(); ++i) {
+    bufs.insert(bufs.end(), batches[i].begin(), batches[i].end());
+    offsets[i + 1] = bufs.size();
+  }
+  std::vector<hsv_batch_result> res(batches.size());
+  crypto::check_infra(hsv_batches_verify_bincode(committee, bufs.data(), offsets.data(), batches.size(), res.data(),
+                                                 nullptr, 0),
+                      "hsv_batches_verify_bincode");
+  return res;
+}
+
+}  // namespace mempool
+
 #endif  // HSV_CRYPTO_HPP_
