@@ -742,6 +742,8 @@ int DeviceCall::begin(const void *d_ptr, void *stream_in, uint32_t *d_fault, Tab
     if (rc == HSV_OK) rc = ensure_btable16(*c);
     comb = c->d_btable;
     comb16 = c->d_btable16;
+  } else if (table == kNone) {
+    return HSV_OK;  // no table and no self-check words either
   } else {  // rebuilt here if hsv_shutdown released it
     rc = table == kNarrow ? ensure_btable(*c) : ensure_btable16(*c);
     comb = table == kNarrow ? c->d_btable : c->d_btable16;

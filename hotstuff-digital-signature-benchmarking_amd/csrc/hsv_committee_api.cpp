@@ -532,6 +532,16 @@ int committee_msgs_indexed_host(const hsv_committee &cm, const uint32_t *key_idx
 // rounds of kChunk in order on `s`, every flag byte written; device c current).
 int committee_device_of(const hsv_committee *cm) { return cm->dev.device; }
 
+CommitteeKeys committee_keys_of(const hsv_committee *cm) {
+  CommitteeKeys k;
+  k.device = cm->dev.device;
+  k.n = cm->dev.n;
+  k.d_keytab = cm->d_keytab;
+  k.keymask = cm->keymask;
+  k.d_pks = cm->dev.d_pks;
+  return k;
+}
+
 int committee_tx_spans_enqueue(const hsv_committee *cm, DevCtx &c, const uint32_t *btable, const uint32_t *comb16,
                                const uint8_t *d_bufs, const uint64_t *d_spans, size_t n, uint8_t *d_flags,
                                uint32_t *d_fault, hipStream_t s) {

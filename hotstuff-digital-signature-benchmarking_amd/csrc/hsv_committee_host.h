@@ -37,6 +37,18 @@ hipError_t build_tables(const uint8_t *d_encs, uint32_t nkeys, uint32_t *const *
 // flag byte of the n transactions is written; device c current, its two B
 // tables ensured by the caller).
 int committee_device_of(const hsv_committee *cm);
+// The handle's key table for the signer census (hsv_census_api.cpp), which
+// leaves a committee's members out: keytab_find's arguments (hsv_keytab.hpp;
+// the table was built under KeyHash::seed()).  n == 0: an empty committee, the
+// pointers are NULL.
+struct CommitteeKeys {
+  int device = 0;
+  uint32_t n = 0;
+  const uint32_t *d_keytab = nullptr;
+  uint32_t keymask = 0;
+  const uint8_t *d_pks = nullptr;
+};
+CommitteeKeys committee_keys_of(const hsv_committee *cm);
 int committee_tx_spans_enqueue(const hsv_committee *cm, DevCtx &c, const uint32_t *btable, const uint32_t *comb16,
                                const uint8_t *d_bufs, const uint64_t *d_spans, size_t n, uint8_t *d_flags,
                                uint32_t *d_fault, hipStream_t s);

@@ -319,8 +319,9 @@ int pointer_device(const void *p);
 class DeviceCall {
  public:
   // ensure_btable, ensure_btable16, comb_table_for(variant()); kBoth: the
-  // narrow table in `comb` and the wide one in `comb16`
-  enum Table { kNarrow, kWide, kVariant, kBoth };
+  // narrow table in `comb` and the wide one in `comb16`; kNone: no table (the
+  // signer census does no curve arithmetic)
+  enum Table { kNarrow, kWide, kVariant, kBoth, kNone };
   int begin(const void *d_ptr, void *stream, uint32_t *d_fault, Table table, const char *owner = nullptr,
             int owner_device = -1);
   DevCtx *c = nullptr;

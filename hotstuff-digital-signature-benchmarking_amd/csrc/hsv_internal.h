@@ -269,6 +269,22 @@ hipError_t hsv_launch_committee_tx(const uint8_t *txs, const uint64_t *offsets, 
                                    const uint8_t *key_flags, uint32_t nkeys, const uint32_t *const *key_tables,
                                    int digit_bits, const uint32_t *btable, const uint32_t *comb16, uint8_t *flags_out,
                                    uint32_t *strict_bits, uint32_t *fault, uint64_t *totals, hipStream_t stream);
+// One signer census (hsv_census_*; hsv_census.hip) on `stream`: the count
+// kernel and the gather kernel over a zeroed workspace of 8 bytes per slot
+// from the library pool.  mode 0: n keys at in + i * stride (both multiples of
+// 16); 1: transactions in[offsets[i], offsets[i + 1]); 2: transactions of
+// `stride` bytes; in at any alignment for 1 and 2.  slots: a power of two in
+// [16, 2^22]; seed: the slot hash's.  keytab / keymask / keyseed / pks / nkeys:
+// the committee whose members are left out (nkeys == 0: none, the arrays may
+// be NULL).  Every entry of keys_out (32 * slots bytes, 16-byte aligned) and
+// counts_out (slots words) and the 48-byte summary are written.
+hipError_t hsv_launch_census(int mode, const uint8_t *in, const uint64_t *offsets, uint64_t stride, uint32_t n,
+                             uint32_t slots, uint64_t seed, const uint32_t *keytab, uint32_t keymask,
+                             uint64_t keyseed, const uint8_t *pks, uint32_t nkeys, uint8_t *keys_out,
+                             uint32_t *counts_out, void *summary, hipStream_t stream);
+// The slot-hash seed of the calling thread's census calls (hsv_test_census_seed,
+// hsv_census_api.cpp): 0 restores the per-process seed.
+void hsvi_set_census_seed(uint64_t seed);
 // Ed25519 over messages of any length (hsv_verify_msgs*): k = SHA-512(R || A
 // || M) over the whole message.  Message i is msgs[offsets[i], offsets[i+1])
 // (offsets != NULL; a decreasing pair gives flags 0) or msg_len bytes at

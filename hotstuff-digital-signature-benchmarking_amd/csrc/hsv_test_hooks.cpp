@@ -96,6 +96,10 @@ int hsv_test_batch_stages(const uint8_t *d_bufs, const uint64_t *d_offsets, size
   return hsvh::batch_stage_times(d_bufs, d_offsets, n_batches, tx_cap, static_cast<hsv_batch_result *>(d_results),
                                  ms_out);
 }
+int hsv_test_census_seed(uint64_t seed) {
+  hsvi_set_census_seed(seed);
+  return HSV_OK;
+}
 size_t hsv_test_stage_bytes(size_t bytes) { return hsvh::g_stage_bytes.exchange(bytes ? bytes : hsvh::kStageBytes); }
 
 }  // extern "C"

@@ -159,6 +159,13 @@ HSV_API int hsv_test_cmsg_indexed_counts(uint64_t out[3]);
  * Synchronises.  HSV_OK or an error. */
 HSV_API int hsv_test_batch_stages(const uint8_t *d_bufs, const uint64_t *d_offsets, size_t n_batches, size_t tx_cap,
                                   void *d_results, float ms_out[4]);
+/* Tests: the seed of the census table's slot hash (hsv_census_*) for the
+ * calling thread's calls, in the place of the per-process random one, so that
+ * a test can choose keys that share a home slot (the hash is keytab_hash of
+ * csrc/hsv_keytab.hpp).  The lookup in a `skip` committee keeps the process
+ * seed, which its table was built under.  0 restores the process seed.
+ * HSV_OK.  Needs no device. */
+HSV_API int hsv_test_census_seed(uint64_t seed);
 
 #ifdef __cplusplus
 }

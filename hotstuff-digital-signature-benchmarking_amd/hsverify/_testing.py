@@ -171,6 +171,13 @@ def committee_tx_counts() -> tuple:
     return int(out[0]), int(out[1]), int(out[2])
 
 
+def census_seed(seed: int) -> None:
+    """The slot-hash seed of the calling thread's census calls (mempool.census*;
+    hsv_test_census_seed, test library): tests choose keys that share a home
+    slot under it.  0 restores the per-process seed."""
+    _lib.check(_lib.hook("hsv_test_census_seed")(ctypes.c_uint64(int(seed))), "hsv_test_census_seed")
+
+
 def committee_msgs_counts() -> tuple:
     """(hits, misses, fallback items) of the calling thread's last
     Committee.verify_msgs* call, summed over its rounds (test library; after

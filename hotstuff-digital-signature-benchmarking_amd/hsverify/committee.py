@@ -36,6 +36,24 @@ class Committee:
         _lib.check(self._lib.hsv_committee_create_ex(_ptr(arr) if arr.size else None, arr.shape[0], 4 if compact else 8,
                                                      ctypes.byref(self._h)), "hsv_committee_create_ex")
         self._n = arr.shape[0]
+        self._keys = arr.copy()  # by member index (learn(skip=...) re-creates a committee from them)
+
+    @classmethod
+    def learn(cls, txs, min_count: int = 2, max_keys: int = 8192, compact: bool = False, skip=None, slots=None):
+        """A committee of the frequent signers of ``txs`` (mempool.census: a
+        sequence of ``bytes`` or an (n, tx_size) array; nothing is verified):
+        the keys that occur at least ``min_count`` times, at most ``max_keys``
+        of them in census order (most frequent first).  With ``skip`` (a
+        Committee) its members are left out of the census and the result holds
+        ``skip``'s keys followed by the new ones.  A committee is immutable --
+        its tables are built once, at creation -- so growing one means
+        creating another; ``skip`` stays valid and is the caller's to close."""
+        from .mempool import census
+        keys, counts, _ = census(txs, skip=skip, slots=slots)
+        new = keys[counts >= min_count][:max_keys]
+        if skip is not None:
+            new = np.concatenate([skip._keys, new]) if new.size else skip._keys
+        return cls(np.ascontiguousarray(new, np.uint8).reshape(-1, 32), compact=compact)
 
     @property
     def digit_bits(self) -> int:

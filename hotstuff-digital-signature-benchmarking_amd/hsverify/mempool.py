@@ -136,3 +136,101 @@ def verify_serialized_batch(buf: bytes, committee=None) -> bool:
             return False
         raise
     return ok
+
+
+# ---- signer census (hsv_census_*) -------------------------------------------------
+# Who signs a batch, and how often: the distinct 32-byte signer keys counted on
+# the GPU, for a node that wants to build the committee of its known clients
+# (committee.Committee.learn) from the transactions it actually sees.
+
+class CensusSummary(ctypes.Structure):
+    """hsv_census_summary (include/hsv.h): items == counted + members +
+    malformed + overflow, always."""
+    _fields_ = [("items", ctypes.c_uint64), ("counted", ctypes.c_uint64), ("members", ctypes.c_uint64),
+                ("malformed", ctypes.c_uint64), ("overflow", ctypes.c_uint64), ("distinct", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
+
+
+def default_census_slots(n: int) -> int:
+    """The next power of two >= 4 x min(n, 2^20), at least 16: load <= 1/4 if
+    every item had a key of its own, up to the table's largest size."""
+    slots = 16
+    while slots < 4 * min(int(n), 1 << 20):
+        slots <<= 1
+    return slots
+
+
+def _check_slots(slots: int) -> int:
+    slots = int(slots)
+    if slots < 16 or slots > (1 << 22) or slots & (slots - 1):
+        raise ValueError("slots must be a power of two in [16, 2^22]")
+    return slots
+
+
+def census(txs, skip=None, slots: int | None = None):
+    """The distinct signer keys of ``txs`` and how often each occurs
+    (``hsv_census_transactions``; nothing is verified).  ``txs``: a sequence of
+    ``bytes`` (ragged) or an ``(n, tx_size)`` uint8 array.  ``skip`` (a
+    committee.Committee): its members are counted in ``members`` and not
+    returned.  ``slots``: the census table's size, a power of two in
+    [16, 2^22]; default :func:`default_census_slots`.  Returns ``(keys (k, 32)
+    uint8, counts (k,) uint32, summary dict)``, sorted by count descending, then
+    key bytes ascending.  A transaction shorter than 96 bytes is counted in
+    ``malformed``."""
+    if isinstance(txs, np.ndarray):
+        arr = np.ascontiguousarray(txs, dtype=np.uint8)
+        if arr.ndim != 2:
+            raise ValueError("expected an (n, tx_size) array")
+        n, size = arr.shape
+        buf, offsets = arr, None
+    else:
+        txs = list(txs)
+        n, size = len(txs), 0
+        buf, offsets = pack(txs)
+    slots = default_census_slots(n) if slots is None else _check_slots(slots)
+    keys = np.zeros((slots, 32), np.uint8)
+    counts = np.zeros(slots, np.uint32)
+    summary = CensusSummary()
+    lib = _lib.load()
+    _lib.check(lib.hsv_census_transactions(skip._h if skip is not None else None, _ptr(buf) if buf.size else None,
+                                           _ptr(offsets) if offsets is not None else None, size, n, slots, _ptr(keys),
+                                           _ptr(counts), slots, ctypes.byref(summary)), "hsv_census_transactions")
+    k = int(summary.distinct)
+    return keys[:k].copy(), counts[:k].copy(), summary.as_dict()
+
+
+def census_device(txs, offsets=None, tx_size: int = 0, n: int | None = None, skip=None, slots: int | None = None,
+                  keys_out=None, counts_out=None, summary_out=None, stream=None):
+    """Enqueue a census of device-resident transactions (torch uint8 tensor
+    ``txs``; ``offsets`` an int64 tensor of n + 1 byte offsets, or None with
+    ``tx_size``), as :func:`verify_transactions_device` addresses them.
+    Outputs (allocated on ``txs``'s device when not given): ``keys_out``
+    (slots, 32) uint8, ``counts_out`` (slots,) int32, ``summary_out`` (6,)
+    int64 -- items, counted, members, malformed, overflow, distinct.  The first
+    ``distinct`` entries are the census, in no particular order; the rest are
+    0.  No synchronisation.  Returns ``(keys_out, counts_out, summary_out)``."""
+    import torch
+
+    if n is None:
+        n = offsets.numel() - 1 if offsets is not None else txs.numel() // tx_size
+    slots = default_census_slots(n) if slots is None else _check_slots(slots)
+    dev = txs.device
+    if keys_out is None:
+        keys_out = torch.empty((slots, 32), dtype=torch.uint8, device=dev)
+    if counts_out is None:
+        counts_out = torch.empty(slots, dtype=torch.int32, device=dev)
+    if summary_out is None:
+        summary_out = torch.empty(6, dtype=torch.int64, device=dev)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    lib = _lib.load()
+    rc = lib.hsv_census_transactions_device(
+        skip._h if skip is not None else None, ctypes.c_void_p(txs.data_ptr()),
+        ctypes.c_void_p(offsets.data_ptr()) if offsets is not None else None, tx_size, n, slots,
+        ctypes.c_void_p(keys_out.data_ptr()), ctypes.c_void_p(counts_out.data_ptr()),
+        ctypes.c_void_p(summary_out.data_ptr()), ctypes.c_void_p(stream))
+    _lib.check(rc, "hsv_census_transactions_device")
+    return keys_out, counts_out, summary_out

@@ -119,7 +119,7 @@ HSV_API const char *hsv_last_error(void);
  * hsv_verify_transactions_device) take the optional d_fault argument before
  * `stream`; a caller built against 0.2.x headers must be rebuilt (check
  * HSV_ABI_VERSION against hsv_abi_version() at startup).  Entry points added
- * since (the last: the serialized-batch calls hsv_batch*_bincode*) change no
+ * since (the last: the signer census hsv_census_*) change no
  * existing signature
  * and leave both the version and HSV_ABI_VERSION as they are. */
 #define HSV_ABI_VERSION 3
@@ -471,6 +471,76 @@ HSV_API int hsv_verify_transactions_fixed(const uint8_t *txs, size_t tx_size, si
  * NULL, not both). */
 HSV_API int hsv_verify_transactions_device(const uint8_t *d_txs, const uint64_t *d_offsets, size_t tx_size, size_t n,
                                    uint8_t *d_flags, uint32_t *d_strict_bits, uint32_t *d_fault, void *stream);
+
+/* ---- signer census: who signs a batch, and how often --------------------- */
+/* hsv_committee_verify_transactions* needs the known clients' keys in an
+ * hsv_committee; a mempool sees only the 32 pk bytes inside each transaction.
+ * The census returns the distinct signer keys of a batch and how often each
+ * occurs, counted on the GPU; the caller builds a committee from the frequent
+ * ones (hsv_committee_create) and passes it to the calls above.  No existing
+ * call changes: the census is explicit and opt-in.
+ * Key: the 32 raw pk bytes.  Of a transaction these are bytes [len - 96,
+ * len - 64), addressed by d_offsets / tx_size exactly as
+ * hsv_verify_transactions_device addresses them, at any byte alignment.
+ * Nothing is decompressed or verified: the census says who signs, not whether
+ * they sign well.  A transaction shorter than 96 bytes, or whose offsets
+ * decrease, is counted in `malformed` and nowhere else.
+ * slots: the size of the census table, a power of two, 16 <= slots <= 2^22
+ * (else HSV_ERR_INVALID_ARG).  Open addressing, linear probing, the slot hash
+ * keyed with the per-process seed (keys are attacker-chosen bytes).  A probe
+ * walk is bounded by min(slots, 256) slots: an item whose key finds neither
+ * itself nor an empty slot within the bound is added to `overflow`, so a flood
+ * of distinct keys cannot turn the call into an n x slots walk.  Slots never
+ * empty: a key is either recorded with its exact count or not recorded at all.
+ * At load <= 1/4 a run of 256 occupied slots does not occur in practice:
+ * size slots >= 4 x the distinct keys you expect.
+ * skip (optional): a key that is a member of `skip` is added to `members` and
+ * not recorded -- "who are the frequent strangers?", for a caller who already
+ * holds a committee.  Full and compact committees alike. */
+typedef struct hsv_census_summary {
+  uint64_t items;     /* n */
+  uint64_t counted;   /* sum of the counts written */
+  uint64_t members;   /* signer is a member of `skip` (0 without one) */
+  uint64_t malformed; /* transaction forms: shorter than 96 bytes or decreasing offsets */
+  uint64_t overflow;  /* the key found no slot (above) */
+  uint32_t distinct;  /* entries written to keys_out / counts_out */
+  uint32_t reserved;  /* 0 */
+} hsv_census_summary; /* items == counted + members + malformed + overflow, always */
+
+/* Device forms: stream-ordered, they never synchronise.  Device and stream as
+ * hsv_verify_transactions_device (the device that owns the inputs; a stream
+ * of another device is HSV_ERR_INVALID_ARG); with skip != NULL the inputs must
+ * lie on its device.  Key form: d_pk and pk_stride are multiples of 16, as in
+ * hsv_verify_device, pk_stride >= 32.  Transaction form: d_offsets (n + 1
+ * entries relative to d_txs) or NULL for fixed tx_size (below 96:
+ * HSV_ERR_INVALID_ARG).  d_keys_out (32 * slots bytes) is 16-byte,
+ * d_counts_out (slots words) and d_summary 8-byte aligned (HSV_ERR_ALIGN).
+ * Every entry of d_keys_out and d_counts_out is written: the first `distinct`
+ * are the census, in no particular order, the rest are 0.  n <= 2^32 - 1;
+ * n == 0 is valid (the inputs may be NULL) and gives an all-zero summary.
+ * Two launches and one memset; the workspace, 8 bytes per slot, is a block of
+ * its own per call from the library's stream-ordered pool.  All argument
+ * errors are reported before any device work. */
+HSV_API int hsv_census_keys_device(const hsv_committee *skip, const uint8_t *d_pk, size_t pk_stride, size_t n,
+                                   uint32_t slots, uint8_t *d_keys_out, uint32_t *d_counts_out,
+                                   hsv_census_summary *d_summary, void *stream);
+HSV_API int hsv_census_transactions_device(const hsv_committee *skip, const uint8_t *d_txs, const uint64_t *d_offsets,
+                                           size_t tx_size, size_t n, uint32_t slots, uint8_t *d_keys_out,
+                                           uint32_t *d_counts_out, hsv_census_summary *d_summary, void *stream);
+/* Host forms: synchronous, on skip's device or else the device a host-buffer
+ * call runs on.  Only the 32 key bytes of each item are staged (a 512-byte
+ * transaction costs 32 bytes of host-to-device copy), at any alignment and
+ * pk_stride >= 32.  The result is sorted by count descending, then key bytes
+ * ascending, so it is deterministic; the first min(distinct, keys_cap) entries
+ * are written to keys_out (32 bytes each) and counts_out, which may be NULL
+ * when keys_cap is 0; summary->distinct is the full number.  n <= 2^22 (above:
+ * HSV_ERR_INVALID_ARG before any device work).  Without a GPU,
+ * HSV_ERR_NO_DEVICE. */
+HSV_API int hsv_census_keys(hsv_committee *skip, const uint8_t *pk, size_t pk_stride, size_t n, uint32_t slots,
+                            uint8_t *keys_out, uint32_t *counts_out, size_t keys_cap, hsv_census_summary *summary);
+HSV_API int hsv_census_transactions(hsv_committee *skip, const uint8_t *txs, const uint64_t *offsets, size_t tx_size,
+                                    size_t n, uint32_t slots, uint8_t *keys_out, uint32_t *counts_out, size_t keys_cap,
+                                    hsv_census_summary *summary);
 
 /* ---- wire formats ---------------------------------- */
 /* Certificates verified straight from their bincode bytes (bincode 1.3
