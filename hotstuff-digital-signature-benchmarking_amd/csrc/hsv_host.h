@@ -379,6 +379,12 @@ int tx_lengths_ok(const uint64_t *offsets, size_t tx_size, size_t n);
 int batch_stage_times(const uint8_t *d_bufs, const uint64_t *d_offsets, size_t n_batches, size_t tx_cap,
                       hsv_batch_result *d_results, float ms_out[4]);
 
+// measurement hook (hsv_test_seal_stages, hsv_seal_api.cpp): the stages of
+// hsv_seal_transactions_device between device events
+int seal_stage_times(const uint8_t *d_txs, const uint64_t *d_offsets, size_t tx_size, size_t n, const uint8_t *d_flags,
+                     uint64_t batch_size, int flush, uint8_t *d_out, size_t out_cap, uint64_t *d_batch_offsets,
+                     size_t batches_cap, uint8_t *d_digests, hsv_seal_summary *d_summary, float ms_out[4]);
+
 // ---- the staged host forms and the argument checks of the generic calls and
 // ---- their committee twins (hsv_tx.cpp, hsv_msgs_api.cpp) ----------------------
 // A step run once on the slot's stream after slot_prepare (the committee's

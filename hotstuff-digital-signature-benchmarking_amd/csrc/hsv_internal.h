@@ -285,6 +285,20 @@ hipError_t hsv_launch_census(int mode, const uint8_t *in, const uint64_t *offset
 // The slot-hash seed of the calling thread's census calls (hsv_test_census_seed,
 // hsv_census_api.cpp): 0 restores the per-process seed.
 void hsvi_set_census_seed(uint64_t seed);
+// One seal (hsv_seal_transactions*; hsv_seal.hip) on `stream`: n transactions
+// addressed as above (offsets, or fixed tx_size when it is NULL; any
+// alignment), kept when flags[i] has HSV_STRICT_OK (flags == NULL: all), cut by
+// the greedy rule at batch_size and laid down as MempoolMessage::Batch messages
+// in out[0, out_cap).  batch_offsets: batches_cap + 1 entries, all written;
+// digests (optional): 32 bytes per batch; summary: a hsv_seal_summary, 8-byte
+// aligned.  Workspace: 20 bytes per transaction and 4 per batch of
+// min(batches_cap, n), a block of its own from the library pool.  marks
+// (optional, measurements): five events recorded before the scan, the cut, the
+// copy and the digest launches and after the last.
+hipError_t hsv_launch_seal(const uint8_t *txs, const uint64_t *offsets, uint64_t tx_size, uint32_t n,
+                           const uint8_t *flags, uint64_t batch_size, int flush, uint8_t *out, uint64_t out_cap,
+                           uint64_t *batch_offsets, uint64_t batches_cap, uint8_t *digests, void *summary,
+                           hipEvent_t *marks, hipStream_t stream);
 // Ed25519 over messages of any length (hsv_verify_msgs*): k = SHA-512(R || A
 // || M) over the whole message.  Message i is msgs[offsets[i], offsets[i+1])
 // (offsets != NULL; a decreasing pair gives flags 0) or msg_len bytes at

@@ -100,6 +100,14 @@ int hsv_test_census_seed(uint64_t seed) {
   hsvi_set_census_seed(seed);
   return HSV_OK;
 }
+int hsv_test_seal_stages(const uint8_t *d_txs, const uint64_t *d_offsets, size_t tx_size, size_t n,
+                         const uint8_t *d_flags, uint64_t batch_size, int flush, uint8_t *d_out, size_t out_cap,
+                         uint64_t *d_batch_offsets, size_t batches_cap, uint8_t *d_digests, void *d_summary,
+                         float ms_out[4]) {
+  return hsvh::seal_stage_times(d_txs, d_offsets, tx_size, n, d_flags, batch_size, flush, d_out, out_cap,
+                                d_batch_offsets, batches_cap, d_digests, static_cast<hsv_seal_summary *>(d_summary),
+                                ms_out);
+}
 size_t hsv_test_stage_bytes(size_t bytes) { return hsvh::g_stage_bytes.exchange(bytes ? bytes : hsvh::kStageBytes); }
 
 }  // extern "C"

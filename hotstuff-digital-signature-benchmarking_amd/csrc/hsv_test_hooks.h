@@ -166,6 +166,15 @@ HSV_API int hsv_test_batch_stages(const uint8_t *d_bufs, const uint64_t *d_offse
  * seed, which its table was built under.  0 restores the process seed.
  * HSV_OK.  Needs no device. */
 HSV_API int hsv_test_census_seed(uint64_t seed);
+/* Measurement only (tools/seal_bench.py): hsv_seal_transactions_device with
+ * its arguments, on the null stream of the buffers' device, with a device event
+ * between its stages: ms_out[0] the scan (three launches), [1] the cut wave,
+ * [2] the two copy launches, [3] the digest launch (0 when d_digests is NULL).
+ * Synchronises.  HSV_OK or that call's error. */
+HSV_API int hsv_test_seal_stages(const uint8_t *d_txs, const uint64_t *d_offsets, size_t tx_size, size_t n,
+                                 const uint8_t *d_flags, uint64_t batch_size, int flush, uint8_t *d_out, size_t out_cap,
+                                 uint64_t *d_batch_offsets, size_t batches_cap, uint8_t *d_digests, void *d_summary,
+                                 float ms_out[4]);
 
 #ifdef __cplusplus
 }

@@ -32,7 +32,8 @@ HOOKS = ("hsv_test_inject_fault", "hsv_test_inject_mode", "hsv_test_corrupt_auto
          "hsv_test_tx_sign_chunk", "hsv_test_msg_sign_chunk", "hsv_test_stage_bytes", "hsv_test_committee_tx_counts",
          "hsv_test_committee_msgs_counts", "hsv_test_msgs_small", "hsv_test_msgs_form_counts",
          "hsv_test_field_ops", "hsv_test_scalar_ops", "hsv_test_cmsg_indexed_form", "hsv_test_cmsg_indexed_counts",
-         "hsv_test_deal", "hsv_test_deal_counts", "hsv_test_batch_stages", "hsv_test_census_seed")
+         "hsv_test_deal", "hsv_test_deal_counts", "hsv_test_batch_stages", "hsv_test_census_seed",
+         "hsv_test_seal_stages")
 
 # flag bits (include/hsv.h)
 STRICT_OK = 0x01
@@ -197,6 +198,14 @@ def _declare(lib):
         "hsv_census_transactions": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u8p, sz, sz, ctypes.c_uint32, c_u8p, c_u8p,
                                                    sz, ctypes.c_void_p]),
         "hsv_test_census_seed": (ctypes.c_int, [ctypes.c_uint64]),
+        "hsv_seal_bound": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                          ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+        "hsv_seal_transactions_device": (ctypes.c_int, [c_u8p, c_u8p, sz, sz, c_u8p, ctypes.c_uint64, ctypes.c_int, c_u8p,
+                                                        sz, c_u8p, sz, c_u8p, ctypes.c_void_p, ctypes.c_void_p]),
+        "hsv_seal_transactions": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u8p, sz, sz, ctypes.c_uint64, ctypes.c_int,
+                                                 c_u8p, sz, c_u8p, sz, c_u8p, c_u8p, ctypes.c_void_p]),
+        "hsv_test_seal_stages": (ctypes.c_int, [c_u8p, c_u8p, sz, sz, c_u8p, ctypes.c_uint64, ctypes.c_int, c_u8p, sz,
+                                                c_u8p, sz, c_u8p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
         "hsv_test_deal": (ctypes.c_int, [ctypes.c_int]),
         "hsv_test_deal_counts": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32)]),
     }
@@ -214,7 +223,8 @@ def _declare(lib):
                              "hsv_vote_verify_bincode", "hsv_blocks_verify_bincode", "hsv_batch_parse_bincode",
                              "hsv_batches_verify_bincode", "hsv_batch_verify_bincode",
                              "hsv_batches_verify_bincode_device", "hsv_census_keys_device",
-                             "hsv_census_transactions_device", "hsv_census_keys", "hsv_census_transactions"}
+                             "hsv_census_transactions_device", "hsv_census_keys", "hsv_census_transactions",
+                             "hsv_seal_bound", "hsv_seal_transactions_device", "hsv_seal_transactions"}
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None) if name in optional else getattr(lib, name)
         if fn is None:

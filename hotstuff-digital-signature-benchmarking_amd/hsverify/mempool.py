@@ -234,3 +234,124 @@ def census_device(txs, offsets=None, tx_size: int = 0, n: int | None = None, ski
         ctypes.c_void_p(summary_out.data_ptr()), ctypes.c_void_p(stream))
     _lib.check(rc, "hsv_census_transactions_device")
     return keys_out, counts_out, summary_out
+
+
+# ---- sealing verified transactions into batches (hsv_seal_*) ------------------------
+# BatchMaker::run / seal on the device: the transactions whose signature verifies,
+# cut by the greedy rule at batch_size and serialized as MempoolMessage::Batch.
+
+SEAL_OK, SEAL_OVERFLOW = 0, 1
+
+
+class SealSummary(ctypes.Structure):
+    """hsv_seal_summary (include/hsv.h): items == sealed + rejected + malformed +
+    held, always."""
+    _fields_ = [("items", ctypes.c_uint64), ("sealed", ctypes.c_uint64), ("rejected", ctypes.c_uint64),
+                ("malformed", ctypes.c_uint64), ("held", ctypes.c_uint64), ("held_first", ctypes.c_uint64),
+                ("bytes", ctypes.c_uint64), ("n_batches", ctypes.c_uint32), ("status", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+    @classmethod
+    def from_words(cls, words) -> "SealSummary":
+        """From the (8,) int64 tensor or array :func:`seal_device` fills."""
+        return cls.from_buffer_copy(np.ascontiguousarray(np.asarray(words), dtype=np.int64).tobytes())
+
+
+def seal_bound(total_tx_bytes: int, n: int, batch_size: int):
+    """``(bytes, batches)``: an ``out_cap`` and a ``batches_cap`` that are never
+    below what sealing ``n`` transactions of ``total_tx_bytes`` bytes needs
+    (``hsv_seal_bound``; no GPU)."""
+    b, k = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    _lib.check(_lib.load().hsv_seal_bound(int(total_tx_bytes), int(n), int(batch_size), ctypes.byref(b),
+                                          ctypes.byref(k)), "hsv_seal_bound")
+    return int(b.value), int(k.value)
+
+
+def seal(txs, batch_size: int, committee=None, flush: bool = True, digests: bool = False):
+    """``BatchMaker::run`` with the check enabled, and ``seal``
+    (batch_maker.rs:78-131): verify ``txs`` (a sequence of ``bytes`` or an
+    ``(n, tx_size)`` uint8 array), keep those that pass, cut them greedily at
+    ``batch_size`` and serialize each batch (``hsv_seal_transactions``).
+    ``flush``: close a last partial batch; otherwise its transactions are held
+    and ``summary["held_first"]`` is the index to resubmit from.  ``committee``
+    as in :func:`filter_transactions`.  Returns ``(batches, flags, summary)``,
+    batches a list of ``bytes``, and with ``digests`` a fourth element, the
+    (n_batches, 32) uint8 array of ``SHA-512(batch)[..32]``."""
+    if isinstance(txs, np.ndarray):
+        arr = np.ascontiguousarray(txs, dtype=np.uint8)
+        if arr.ndim != 2:
+            raise ValueError("expected an (n, tx_size) array")
+        n, size = arr.shape
+        buf, offsets = arr, None
+        total = n * size
+    else:
+        txs = list(txs)
+        n, size = len(txs), 0
+        buf, offsets = pack(txs)
+        total = int(offsets[-1])
+    cap, bcap = seal_bound(total, n, batch_size)
+    out = np.zeros(max(cap, 1), np.uint8)
+    boff = np.zeros(bcap + 1, np.uint64)
+    dig = np.zeros((max(bcap, 1), 32), np.uint8) if digests else None
+    flags = np.zeros(max(n, 1), np.uint8)
+    summary = SealSummary()
+    lib = _lib.load()
+    _lib.check(lib.hsv_seal_transactions(committee._h if committee is not None else None,
+                                         _ptr(buf) if buf.size else None,
+                                         _ptr(offsets) if offsets is not None else None, size, n, int(batch_size),
+                                         1 if flush else 0, _ptr(out), cap, _ptr(boff), bcap,
+                                         _ptr(dig) if digests else None, _ptr(flags), ctypes.byref(summary)),
+               "hsv_seal_transactions")
+    if summary.status != SEAL_OK:
+        raise _lib.HsvLibraryError("hsv_seal_transactions: the bound was too small")
+    k = int(summary.n_batches)
+    batches = [out[int(boff[b]):int(boff[b + 1])].tobytes() for b in range(k)]
+    res = (batches, flags[:n].copy(), summary.as_dict())
+    return res + (dig[:k].copy(),) if digests else res
+
+
+def seal_device(txs, offsets=None, tx_size: int = 0, n: int | None = None, flags=None, batch_size: int = 500_000,
+                flush: bool = True, out=None, batch_offsets=None, digests=None, summary_out=None, stream=None):
+    """Enqueue the seal of device-resident transactions (torch uint8 tensor
+    ``txs``; ``offsets`` an int64 tensor of n + 1 byte offsets, or None with
+    ``tx_size``), as :func:`verify_transactions_device` addresses them, with
+    the ``flags`` (n,) uint8 any verify call wrote (None: keep everything).
+    ``out`` (uint8) and ``batch_offsets`` (int64, batches_cap + 1 entries) are
+    allocated by :func:`seal_bound` when not given (fixed size only: a ragged
+    batch's byte total is on the device); ``digests``: None, or a
+    (batches_cap, 32) uint8 tensor, or True to allocate one; ``summary_out``
+    (8,) int64, read with :meth:`SealSummary.from_words`.  No synchronisation.
+    Returns ``(out, batch_offsets, digests, summary_out)``."""
+    import torch
+
+    if n is None:
+        n = offsets.numel() - 1 if offsets is not None else txs.numel() // tx_size
+    dev = txs.device
+    if out is None or batch_offsets is None:
+        if offsets is not None:
+            raise ValueError("a ragged batch needs out and batch_offsets (seal_bound of its byte total)")
+        cap, bcap = seal_bound(n * tx_size, n, batch_size)
+        if out is None:
+            out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+        if batch_offsets is None:
+            batch_offsets = torch.empty(bcap + 1, dtype=torch.int64, device=dev)
+    bcap = batch_offsets.numel() - 1
+    if digests is True:
+        digests = torch.empty((max(bcap, 1), 32), dtype=torch.uint8, device=dev)
+    if digests is not None and digests.numel() < 32 * bcap:
+        raise ValueError("digests holds fewer than batches_cap entries")
+    if summary_out is None:
+        summary_out = torch.empty(8, dtype=torch.int64, device=dev)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    lib = _lib.load()
+    rc = lib.hsv_seal_transactions_device(
+        ctypes.c_void_p(txs.data_ptr()), ctypes.c_void_p(offsets.data_ptr()) if offsets is not None else None,
+        tx_size, n, ctypes.c_void_p(flags.data_ptr()) if flags is not None else None, int(batch_size),
+        1 if flush else 0, ctypes.c_void_p(out.data_ptr()), out.numel(), ctypes.c_void_p(batch_offsets.data_ptr()),
+        bcap, ctypes.c_void_p(digests.data_ptr()) if digests is not None else None,
+        ctypes.c_void_p(summary_out.data_ptr()), ctypes.c_void_p(stream))
+    _lib.check(rc, "hsv_seal_transactions_device")
+    return out, batch_offsets, digests, summary_out
