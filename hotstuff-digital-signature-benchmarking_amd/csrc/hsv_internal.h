@@ -404,6 +404,21 @@ hipError_t hsv_launch_batch_scan(const uint8_t *bufs, const uint64_t *offsets, u
                                  hipStream_t stream);
 hipError_t hsv_launch_batch_reduce(const uint32_t *status, const uint64_t *count, const uint64_t *first,
                                    const uint8_t *flags, uint32_t n_batches, void *results, hipStream_t stream);
+
+// ---- the benchmark's sample transactions (hsv_samples.hip) -------------------
+// The sample index of the same batches (hsv_batches_samples_bincode_device): a
+// memset of the span table, hsv_launch_batch_scan and four launches on `stream`.
+// index: n_batches hsv_batch_samples, 8-byte aligned; ids: ids_cap 8-byte words,
+// of which only those below the call's sample count are written.  Workspace:
+// 20 bytes per transaction of tx_cap (<= 2^32 - 1) and 20 per batch, a block of
+// its own from the library pool.
+hipError_t hsv_launch_batch_samples(const uint8_t *bufs, const uint64_t *offsets, uint32_t n_batches, uint64_t tx_cap,
+                                    void *index, uint64_t *ids, uint64_t ids_cap, hipStream_t stream);
+// The client's transactions (hsv_client_bursts_device): one launch, bytes
+// [0, tx_size - trailer) of n <= 2^32 - 1 transactions at txs + i * tx_size, any
+// alignment; burst > 0 and tx_size - trailer >= 9.
+hipError_t hsv_launch_client_bursts(uint8_t *txs, uint64_t tx_size, uint64_t trailer, uint64_t counter0,
+                                    uint64_t burst, uint64_t r0, uint64_t n, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -206,6 +206,13 @@ def _declare(lib):
                                                  c_u8p, sz, c_u8p, sz, c_u8p, c_u8p, ctypes.c_void_p]),
         "hsv_test_seal_stages": (ctypes.c_int, [c_u8p, c_u8p, sz, sz, c_u8p, ctypes.c_uint64, ctypes.c_int, c_u8p, sz,
                                                 c_u8p, sz, c_u8p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
+        "hsv_batch_samples_bincode": (ctypes.c_int, [c_u8p, sz, ctypes.c_void_p, c_u8p, sz]),
+        "hsv_batches_samples_bincode_device": (ctypes.c_int, [c_u8p, c_u8p, sz, sz, ctypes.c_void_p, c_u8p, sz,
+                                                              ctypes.c_void_p]),
+        "hsv_client_bursts": (ctypes.c_int, [c_u8p, sz, sz, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, sz,
+                                             ctypes.POINTER(ctypes.c_uint64)]),
+        "hsv_client_bursts_device": (ctypes.c_int, [c_u8p, sz, sz, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                                    sz, ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]),
         "hsv_test_deal": (ctypes.c_int, [ctypes.c_int]),
         "hsv_test_deal_counts": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32)]),
     }
@@ -224,7 +231,9 @@ def _declare(lib):
                              "hsv_batches_verify_bincode", "hsv_batch_verify_bincode",
                              "hsv_batches_verify_bincode_device", "hsv_census_keys_device",
                              "hsv_census_transactions_device", "hsv_census_keys", "hsv_census_transactions",
-                             "hsv_seal_bound", "hsv_seal_transactions_device", "hsv_seal_transactions"}
+                             "hsv_seal_bound", "hsv_seal_transactions_device", "hsv_seal_transactions",
+                             "hsv_batch_samples_bincode", "hsv_batches_samples_bincode_device", "hsv_client_bursts",
+                             "hsv_client_bursts_device"}
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None) if name in optional else getattr(lib, name)
         if fn is None:

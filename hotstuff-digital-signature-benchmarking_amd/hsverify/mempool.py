@@ -355,3 +355,81 @@ def seal_device(txs, offsets=None, tx_size: int = 0, n: int | None = None, flags
         ctypes.c_void_p(summary_out.data_ptr()), ctypes.c_void_p(stream))
     _lib.check(rc, "hsv_seal_transactions_device")
     return out, batch_offsets, digests, summary_out
+
+
+# ---- the benchmark's sample transactions (hsv_batch_samples_bincode*) ----------------
+# What the `benchmark` block of BatchMaker::seal logs about a batch
+# (batch_maker.rs:118-125, 133-153): the ids of its sample transactions (first
+# byte 0, longer than 8 bytes; the id is bytes 1..9 big-endian) and its size,
+# the sum of the transactions' lengths.  hsverify.benchlog formats the lines.
+
+BATCH_OK, BATCH_TX, BATCH_PARSE, BATCH_OVERFLOW = 0, 1, 2, 3
+
+
+class BatchSamples(ctypes.Structure):
+    """hsv_batch_samples (include/hsv.h), 40 bytes."""
+    _fields_ = [("status", ctypes.c_uint32), ("pad", ctypes.c_uint32), ("n_tx", ctypes.c_uint64),
+                ("size", ctypes.c_uint64), ("n_samples", ctypes.c_uint64), ("first_sample", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "pad"}
+
+    @classmethod
+    def from_words(cls, words) -> "BatchSamples":
+        """From one (5,) int64 row of the index :func:`batches_samples_device` fills."""
+        return cls.from_buffer_copy(np.ascontiguousarray(np.asarray(words), dtype=np.int64).tobytes())
+
+
+def batch_samples(buf: bytes, count_only: bool = False):
+    """The sample index of one serialized ``MempoolMessage::Batch`` on the host
+    (``hsv_batch_samples_bincode``; no GPU).  Returns ``(summary dict, ids)``,
+    ids a (n_samples,) uint64 array in transaction order, or None with
+    ``count_only``.  Raises HsvLibraryError (HSV_ERR_PARSE) for malformed bytes."""
+    buf = bytes(buf)
+    lib = _lib.load()
+    res = BatchSamples()
+    _lib.check(lib.hsv_batch_samples_bincode(buf, len(buf), ctypes.byref(res), None, 0), "hsv_batch_samples_bincode")
+    if count_only:
+        return res.as_dict(), None
+    ids = np.zeros(max(int(res.n_samples), 1), np.uint64)
+    _lib.check(lib.hsv_batch_samples_bincode(buf, len(buf), ctypes.byref(res), _ptr(ids), int(res.n_samples)),
+               "hsv_batch_samples_bincode")
+    return res.as_dict(), ids[:int(res.n_samples)].copy()
+
+
+def batches_samples_device(bufs, offsets, tx_cap: int, n_batches: int | None = None, index=None, ids=None,
+                           stream=None):
+    """Enqueue the sample index of device-resident serialized batches (torch
+    uint8 tensor ``bufs``; ``offsets`` an int64 tensor of n_batches + 1 byte
+    offsets), parsed as ``hsv_batches_verify_bincode_device`` parses them.
+    ``(out, batch_offsets)`` of :func:`seal_device` can be passed whole, with
+    ``tx_cap`` the seal's n: the entries past the real batch count come out as
+    BATCH_PARSE with no ids.  Outputs (allocated on ``bufs``'s device when not
+    given): ``index`` (n_batches, 5) int64 -- status | pad << 32, n_tx, size,
+    n_samples, first_sample per batch, read with :meth:`BatchSamples.from_words`
+    -- and ``ids`` int64 (the ids' bit patterns; default ``tx_cap`` entries,
+    which always suffices), of which only the first total-sample-count entries
+    are written.  No synchronisation.  Returns ``(index, ids)``."""
+    import torch
+
+    if n_batches is None:
+        n_batches = offsets.numel() - 1
+    dev = bufs.device
+    if index is None:
+        index = torch.empty((max(n_batches, 1), 5), dtype=torch.int64, device=dev)
+    if ids is None:
+        ids = torch.empty(max(int(tx_cap), 1), dtype=torch.int64, device=dev)
+        ids_cap = int(tx_cap)
+    else:
+        ids_cap = ids.numel()
+    if index.numel() < 5 * n_batches:
+        raise ValueError("index holds fewer than n_batches entries")
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    lib = _lib.load()
+    rc = lib.hsv_batches_samples_bincode_device(
+        ctypes.c_void_p(bufs.data_ptr()), ctypes.c_void_p(offsets.data_ptr()), n_batches, int(tx_cap),
+        ctypes.c_void_p(index.data_ptr()), ctypes.c_void_p(ids.data_ptr()) if ids_cap else None, ids_cap,
+        ctypes.c_void_p(stream))
+    _lib.check(rc, "hsv_batches_samples_bincode_device")
+    return index, ids

@@ -241,6 +241,59 @@ def transactions_gpu(n: int, tx_size: int = 512, seed: int = 0) -> TxWorkload:
     return TxWorkload(txs, np.ones(n, bool), np.full(n, -1, np.int8), np.ones(n, bool))
 
 
+def client_bursts(n: int, tx_size: int, burst: int, counter0: int = 0, r0: int = 0, trailer: int = 96,
+                  out: np.ndarray | None = None):
+    """The benchmark client's transactions (node/src/client.rs:106-148;
+    ``hsv_client_bursts``, no GPU): n transactions of tx_size bytes in bursts of
+    ``burst``, burst j carrying exactly one sample ``00 || BE64(counter0 + j)`` at
+    position ``(counter0 + j) % burst`` and otherwise ``01 || BE64(r)`` with a
+    running r that starts after ``r0``; zero padding up to the last ``trailer``
+    bytes, which are left as they are (96: room for ``Signer.sign_transactions``;
+    0: the reference's unsigned filler).  ``out``: an (n, tx_size) uint8 array to
+    fill in place (default: zeros).  Returns ``(txs, r_next)``."""
+    import ctypes
+    from . import _lib
+    if out is None:
+        out = np.zeros((n, tx_size), np.uint8)
+    if out.shape != (n, tx_size) or out.dtype != np.uint8 or not out.flags.c_contiguous:
+        raise ValueError("out must be a contiguous (n, tx_size) uint8 array")
+    r = ctypes.c_uint64(0)
+    _lib.check(_lib.load().hsv_client_bursts(ctypes.c_void_p(out.ctypes.data), int(tx_size), int(trailer),
+                                             int(counter0) % 2**64, int(burst), int(r0) % 2**64, int(n),
+                                             ctypes.byref(r)), "hsv_client_bursts")
+    return out, int(r.value)
+
+
+def client_bursts_gpu(n: int, tx_size: int, burst: int, counter0: int = 0, r0: int = 0, trailer: int = 96,
+                      signer=None, key_idx=None, out=None, stream=None, fault=None):
+    """:func:`client_bursts` on the device (``hsv_client_bursts_device``): the
+    transactions are written into ``out`` (a torch uint8 tensor of n * tx_size
+    bytes at any byte address; default: zeros on the current device) and, with
+    ``signer`` (a signer.Signer), signed there by
+    ``Signer.sign_transactions_device`` with ``key_idx`` (None: key i signs
+    transaction i) -- which needs ``trailer`` >= 96.  Stream-ordered, no
+    synchronisation.  Returns ``(txs (n, tx_size), r_next)``."""
+    import ctypes
+    import torch
+    from . import _lib
+    if out is None:
+        out = torch.zeros((n, tx_size), dtype=torch.uint8, device=torch.device("cuda", torch.cuda.current_device()))
+    if out.numel() != n * tx_size:
+        raise ValueError("out must hold n * tx_size bytes")
+    if signer is not None and trailer < 96:
+        raise ValueError("signing needs the last 96 bytes: trailer >= 96")
+    r = ctypes.c_uint64(0)
+    with torch.cuda.device(out.device):
+        s = torch.cuda.current_stream(out.device).cuda_stream if stream is None else stream
+        _lib.check(_lib.load().hsv_client_bursts_device(ctypes.c_void_p(out.data_ptr()), int(tx_size), int(trailer),
+                                                        int(counter0) % 2**64, int(burst), int(r0) % 2**64, int(n),
+                                                        ctypes.byref(r), ctypes.c_void_p(s)),
+                   "hsv_client_bursts_device")
+    if signer is not None and n:
+        signer.sign_transactions_device(out, tx_size=tx_size, key_idx=key_idx, stream=stream, fault=fault)
+    return out.view(n, tx_size) if out.is_contiguous() else out, int(r.value)
+
+
 def messages_gpu(lens, seed: int = 0):
     """Whole messages of the given byte lengths (some may be 0), one fresh key
     per item, signed on the GPU in one `Signer.sign_msgs_device` call -- the

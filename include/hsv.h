@@ -121,7 +121,8 @@ HSV_API const char *hsv_last_error(void);
  * hsv_verify_transactions_device) take the optional d_fault argument before
  * `stream`; a caller built against 0.2.x headers must be rebuilt (check
  * HSV_ABI_VERSION against hsv_abi_version() at startup).  Entry points added
- * since (the last: the signer census hsv_census_*) change no
+ * since (the last: the benchmark's sample transactions,
+ * hsv_batch_samples_bincode* and hsv_client_bursts*) change no
  * existing signature
  * and leave both the version and HSV_ABI_VERSION as they are. */
 #define HSV_ABI_VERSION 3
@@ -848,6 +849,104 @@ HSV_API int hsv_seal_transactions(hsv_committee *c, const uint8_t *txs, const ui
                                   size_t n, uint64_t batch_size, int flush, uint8_t *out, size_t out_cap,
                                   uint64_t *batch_offsets_out, size_t batches_cap, uint8_t *digests_out,
                                   uint8_t *flags_out, hsv_seal_summary *summary);
+
+/* ---- the benchmark's sample transactions -----------------------------------
+ * The reference measures itself through sample transactions.  Its client
+ * (node/src/client.rs:106-148) puts exactly one into every burst: byte 0, then
+ * the burst counter as a big-endian u64; every other transaction is byte 1, then
+ * a running r; both zero-padded to the transaction size.  BatchMaker::seal
+ * (mempool/src/batch_maker.rs:118-125, 133-153, feature `benchmark`) picks the
+ * samples out of each batch -- tx[0] == 0 && tx.len() > 8, the id bytes 1..9
+ * big-endian -- and logs "Batch {digest:?} contains sample tx {id}" for each and
+ * "Batch {digest:?} contains {size} B" for the batch, size being the sum of the
+ * transactions' lengths (current_batch_size); benchmark/benchmark/logs.py
+ * computes TPS and latency from those lines and the client's "Sending sample
+ * transaction {counter}".  The two calls below are those two ends for a
+ * device-resident pipeline: client bursts -> hsv_signer_sign_transactions_device
+ * -> a verify call -> hsv_seal_transactions_device -> the sample index, with no
+ * batch copied to the host to be walked there.
+ *
+ * Sample index.  A transaction is a sample iff its length is > 8 and its first
+ * byte is 0.  An empty transaction is not a sample (the reference's tx[0] would
+ * panic on one; a batch from the store is untrusted bytes).  Ids are the bytes
+ * 1..9 read big-endian at any byte alignment, in batch order and in transaction
+ * order inside a batch. */
+typedef struct hsv_batch_samples {
+  uint32_t status, pad;  /* HSV_BATCH_OK / HSV_BATCH_PARSE / HSV_BATCH_OVERFLOW; pad = 0 */
+  uint64_t n_tx;         /* as hsv_batch_result */
+  uint64_t size;         /* sum of the transactions' lengths: what seal() logs as "contains {} B" */
+  uint64_t n_samples;    /* transactions with len > 8 and byte 0 == 0 */
+  uint64_t first_sample; /* index of this batch's first id in the ids array */
+} hsv_batch_samples;     /* 40 bytes */
+
+/* Host form, one batch; needs no GPU (like hsv_batch_parse_bincode).  1 = the
+ * batch is well-formed and res (optional) is written, HSV_ERR_PARSE otherwise.
+ * ids_out == NULL only counts; a non-NULL ids_out with ids_cap < n_samples is
+ * HSV_ERR_INVALID_ARG with res still written (and the first ids_cap ids).
+ * first_sample is 0. */
+HSV_API int hsv_batch_samples_bincode(const uint8_t *buf, size_t len, hsv_batch_samples *res, uint64_t *ids_out,
+                                      size_t ids_cap);
+/* Device form: stream-ordered, never synchronises.  Batch b is
+ * d_bufs[d_offsets[b] .. d_offsets[b+1]), parsed exactly as
+ * hsv_batches_verify_bincode_device parses it: the same malformed rules, the same
+ * meaning of tx_cap, the same HSV_BATCH_OVERFLOW; arguments, device ownership
+ * and stream checks as there (n_batches or tx_cap above 2^32 - 1:
+ * HSV_ERR_INVALID_ARG).  d_offsets, d_index (n_batches entries) and d_ids
+ * (ids_cap entries; may be NULL when ids_cap == 0) are 8-byte aligned, else
+ * HSV_ERR_ALIGN.  n_batches == 0 is valid and writes nothing.
+ * first_sample and n_samples are exact whatever ids_cap is: an id whose position
+ * is >= ids_cap is not written, nothing is written at or beyond d_ids + ids_cap,
+ * and positions between the call's sample count and ids_cap are left untouched.
+ * ids_cap = tx_cap always suffices.  A malformed batch gets HSV_BATCH_PARSE and
+ * zeros elsewhere.  A batch whose transactions do not all lie below tx_cap gets
+ * HSV_BATCH_OVERFLOW: n_tx and size are still exact (size = length - 12 -
+ * 8 n_tx, which the parse knows), n_samples is 0, it contributes no ids, and
+ * first_sample is where they would have begun; earlier batches are complete.
+ * (d_out, d_batch_offsets) of hsv_seal_transactions_device can be passed whole,
+ * with n_batches = batches_cap and tx_cap = the seal's n: the repeated end
+ * offsets past the real count are zero-length batches, which come out as
+ * HSV_BATCH_PARSE with no ids -- a device pipeline calls this without reading
+ * the seal's n_batches back.  The seal's digests are the {digest} of the log
+ * lines, entry for entry.
+ * The parse (hsv_launch_batch_scan, as in the verify call), then four launches
+ * (csrc/hsv_samples.hip): one lane per transaction reads its span and first
+ * byte, an ordered compaction over the whole call (a workgroup scan, a scan of
+ * the workgroup sums, an apply pass that writes the ids), and one lane per batch.
+ * No workgroup waits for another.  The workspace, 20 bytes per transaction of
+ * tx_cap and 20 per batch, is a block of its own per call from the library's
+ * stream-ordered pool.
+ * What it costs (profiles/samples_bench.json, one MI355X: 2^20 transactions of
+ * 512 B from hsv_client_bursts_device with burst 1000, sealed at batch_size
+ * 500,000 into 1074 batches; medians, one run): 0.87 ms for the seal's whole
+ * output, 0.26 x the seal (3.34 ms) and 0.077 x hsv_batches_verify_bincode_device
+ * on the same batches (11.40 ms); most of it is the device parse that call pays
+ * as well.  The bursts themselves take 0.134 ms per 2^20, 1.49 x a hipMemsetAsync
+ * of the bytes they write and 0.07 x signing them (1.82 ms). */
+HSV_API int hsv_batches_samples_bincode_device(const uint8_t *d_bufs, const uint64_t *d_offsets, size_t n_batches,
+                                               size_t tx_cap, hsv_batch_samples *d_index, uint64_t *d_ids,
+                                               size_t ids_cap, void *stream);
+
+/* The client's bursts (client.rs:106-148).  Transaction i lies at txs + i *
+ * tx_size, at any alignment.  It belongs to burst j = i / burst with counter
+ * c = counter0 + j (mod 2^64), at position x = i % burst, and is that burst's
+ * sample iff x == c % burst.  A sample is 00 || BE64(c); any other transaction is
+ * 01 || BE64(r) with r = r0 + (the number of non-sample transactions among
+ * 0..i inclusive), mod 2^64 -- the reference's `r += 1` before the write.  Bytes
+ * [9, tx_size - trailer) are zero; the last `trailer` bytes are never written:
+ * trailer = 96 leaves room for hsv_signer_sign_transactions*, trailer = 0 is the
+ * reference's unsigned filler.  n need not be a multiple of burst.  *r_out
+ * (optional) is the r to continue with (the counter to continue with is
+ * counter0 + n / burst, when n is a multiple of burst); it is computed on the
+ * host in closed form in both forms.  burst == 0 or tx_size < 9 + trailer is HSV_ERR_INVALID_ARG (the
+ * reference's size >= 9 check), as are n > 2^32 - 1 and a NULL txs with n > 0;
+ * n == 0 does nothing.  The host form needs no GPU.  The device form is one
+ * stream-ordered launch (sixteen lanes per transaction, 16-byte stores where the
+ * destination allows), never synchronises, and checks device ownership and the
+ * stream as hsv_verify_transactions_device. */
+HSV_API int hsv_client_bursts(uint8_t *txs, size_t tx_size, size_t trailer, uint64_t counter0, uint64_t burst,
+                              uint64_t r0, size_t n, uint64_t *r_out);
+HSV_API int hsv_client_bursts_device(uint8_t *d_txs, size_t tx_size, size_t trailer, uint64_t counter0,
+                                     uint64_t burst, uint64_t r0, size_t n, uint64_t *r_out, void *stream);
 
 /* ---- signing (host CPU; not on the hot path) ---------------------------- */
 /* Public key for a 32-byte secret seed (dalek Keypair from SecretKey). */

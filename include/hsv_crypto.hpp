@@ -771,6 +771,52 @@ inline std::vector<hsv_batch_result> verify_serialized_batches(const std::vector
   return res;
 }
 
+// What the `benchmark` block of BatchMaker::seal logs about a batch
+// (mempool/src/batch_maker.rs:118-125, 133-153; hsv_batch_samples_bincode, no
+// GPU): the ids of its sample transactions in order (ids, optional) and, in the
+// result, their number and the batch's size.  A malformed batch has status
+// HSV_BATCH_PARSE and no ids.  Infrastructure errors throw.
+inline hsv_batch_samples batch_samples(const uint8_t *buf, size_t len, std::vector<uint64_t> *ids = nullptr) {
+  hsv_batch_samples r{};
+  if (ids) ids->clear();
+  int rc = hsv_batch_samples_bincode(buf, len, &r, nullptr, 0);
+  if (rc == 1 && ids && r.n_samples) {
+    ids->resize((size_t)r.n_samples);
+    rc = hsv_batch_samples_bincode(buf, len, &r, ids->data(), ids->size());
+  }
+  if (rc == HSV_ERR_PARSE) {
+    r = hsv_batch_samples{};
+    r.status = HSV_BATCH_PARSE;
+  } else {
+    crypto::check_infra(rc, "hsv_batch_samples_bincode");
+  }
+  return r;
+}
+inline hsv_batch_samples batch_samples(const std::vector<uint8_t> &buf, std::vector<uint64_t> *ids = nullptr) {
+  return batch_samples(buf.data(), buf.size(), ids);
+}
+
 }  // namespace mempool
+
+// The benchmark client's transactions (node/src/client.rs:106-148;
+// hsv_client_bursts, no GPU).
+namespace client {
+
+// n transactions of tx_size bytes in bursts of `burst`, one sample 00 || BE64(counter)
+// per burst among 01 || BE64(r) fillers, zero-padded up to the last `trailer`
+// bytes (96: room for hsv::Signer::sign_transactions; 0: the reference's
+// unsigned filler), which stay zero here.  r (optional): in, the r before the
+// first transaction; out, the r to continue with.
+inline std::vector<uint8_t> bursts(size_t n, size_t tx_size, uint64_t burst, uint64_t counter0 = 0,
+                                   uint64_t *r = nullptr, size_t trailer = 96) {
+  std::vector<uint8_t> txs(n * tx_size, 0);
+  uint64_t r_next = 0;
+  crypto::check_infra(hsv_client_bursts(txs.data(), tx_size, trailer, counter0, burst, r ? *r : 0, n, &r_next),
+                      "hsv_client_bursts");
+  if (r) *r = r_next;
+  return txs;
+}
+
+}  // namespace client
 
 #endif  // HSV_CRYPTO_HPP_
